@@ -8,9 +8,16 @@ derivatives + the config's noise densities) whose camera images are ray-cast fro
 (uvio_amd/render.py) and are resident in HBM before the timed region.  One step = one camera frame: the IMU
 samples since the last frame, then VioManager::feed_measurement_camera (TrackKLT on the device: equalizeHist,
 pyramid, FAST grid detection, cornerSubPix, stereo + temporal pyramidal LK, RANSAC) -> propagate + clone ->
-MSCKF update -> SLAM update / delayed init -> marginalize.  The same frames are then fed once more as host
-images (uvio_hp_feed_camera, the reference caller's form: the library uploads them) into a second estimator;
-that rate is reported as "host_feed" (PCIe-inclusive, never "value").
+MSCKF update -> SLAM update / delayed init -> marginalize.
+
+A plain run does only that: set up, warm up, time --steps frames, write --dump-outputs, print the line.  --full
+adds the companion measurements, each a run of its own after the timed region ("host_feed", "msckf_load",
+"feature_sharded" and "cpu_baseline" below; null in a plain run's line).  With --full the same frames are fed
+once more as host images (uvio_hp_feed_camera, the reference caller's form: the library uploads them) into a
+second estimator; that rate is reported as "host_feed" (PCIe-inclusive, never "value").
+
+--dump-outputs DIR writes, after the timed steps, what the caller of the timed path holds at its last step as
+DIR/<name>.npy (dump_outputs below); the stream is seeded, so equal arguments give equal inputs in every run.
 
 Steady state: the warm-up runs at least --warmup frames and then until the clone window is full
 (max_clones + 1 clones at update time) and the SLAM slots are >= 90 % populated (at most --max-warmup
@@ -19,8 +26,8 @@ frames); the line reports the effective warm-up and whether steady state was rea
 Multi-GPU (--gpus N > 1; launched either by torch.distributed.run, or by this script itself, which then
 spawns N worker processes before any GPU call): value = one independent cfg3 estimator per GPU (the N = 1
 workload on every rank, seed 5 + rank; scaling "weak", value = all ranks' frames / the slowest rank's time), so
-the per-N values of one command compare like with like.  In the same job the line's "feature_sharded" object
-measures the north star's feature-sharded update: every rank runs the same BASELINE stream --
+the per-N values of one command compare like with like.  With --full the line's "feature_sharded" object, in
+the same job, measures the north star's feature-sharded update: every rank runs the same BASELINE stream --
 cfg4 (UZH-FPV, 25 clones x 800 features per update) at N <= 4, cfg5 (rpng_sim 4 cameras + UWB, 30 clones x 1500
 features) at N > 4 -- and each MSCKF update's per-feature linearization, chi2 gate and Gram are split across the
 ranks with one RCCL all-reduce (scaling "strong"), next to rank 0's unsharded time on the same stream.  --shard
@@ -31,7 +38,7 @@ Other workloads (--workload, SURVEY.md §8 cfg 1-5; parity-test cases and stress
   cfg2  EuRoC V1_02-shaped stereo 752x480 images (configs/euroc_mav), 11 clones, <= 200 MSCKF + 50 SLAM
   cfg2l cfg2 with track loss (scene churn: each texture panel redraws every 8 frames), 400 tracks
   cfg3t cfg3's rig and window with a TrackSIM feed at BASELINE's MSCKF load: 400 features per update, each seen
-        in every clone by both cameras (the N = 1 line's "msckf_load" companion, --msckf-load-steps)
+        in every clone by both cameras (the N = 1 line's "msckf_load" companion, --full --msckf-load-steps)
   cfg4 / cfg5  the backend stress at BASELINE's feature counts: TrackSIM feed with 800 / 1500 MSCKF features
         per update, each seen in every clone (26 clones x 2 cameras / 31 clones x 1 of 4 cameras, + 6 UWB
         anchors and IMU intrinsics + g-sensitivity at cfg5) -- the shapes BASELINE.json's cfg4 / cfg5 name
@@ -47,8 +54,8 @@ achieved = algorithmic FLOPs (FP64 classes) or bytes (tracker classes) of the cl
 time in this run (the EKF-update chain aggregate excluded, its LDL factor is its own class), "rooflines" lists
 every class.  traffic = HBM bytes per launch from the committed rocprofv3 PMC passes of the same workload
 (profiles/, FETCH_SIZE x 2 + WRITE_SIZE); mfma_util = SQ_VALU_MFMA_BUSY_CYCLES of the class's kernels over
-(launch duration x shader clock x 256 CUs), from the same committed passes.  cpu_baseline: the oracle/ CPU
-restatement on a bounded sample of the same stream, rank 0 only.  ate: posyaw-aligned ATE RMSE against the
+(launch duration x shader clock x 256 CUs), from the same committed passes.  cpu_baseline (--full): the oracle/
+CPU restatement on a bounded sample of the same stream, rank 0 only.  ate: posyaw-aligned ATE RMSE against the
 stream's ground truth (ov_eval's definition, uvio_amd/evaluation.py).
 """
 import argparse
@@ -473,6 +480,13 @@ def main():
     ap.add_argument("--ktime-period", type=int, default=None,
                     help="kernel-class event timing on every k-th frame of the timed region (0 = off; default: every "
                          "frame for --steps <= 50, else every 10th)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the companion measurements, each a run of its own after the timed region: host_feed, "
+                         "msckf_load, feature_sharded (N > 1) and cpu_baseline (each still has its own switch above); "
+                         "without it the line holds null for them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step's caller reads back (IMU state, state vector, "
+                         "covariance, tracks) as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "0"))
@@ -600,16 +614,19 @@ def main():
     acc_ate = ate_fn(est_p, gt_p, est_q, gt_q, align="posyaw")
     raw = ate_fn(est_p, gt_p, align="none")
     ntr = sum(len(mgr.get_tracks(c)[0]) for c in range(opts.num_cameras)) if images else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, mgr, rec, int(opts.num_cameras) if images else 0)
+    # the companion runs (--full): each sets up and times an estimator of its own
     host_feed = None
-    if frames is not None and world == 1 and not args.no_host_feed:
+    if args.full and frames is not None and world == 1 and not args.no_host_feed:
         mgr.close()
         host_feed = host_feed_pass(U, opts, sim, frames, warm, args.steps, barrier, x_ref=[r[2] for r in rec])
     msckf_load = None
-    if world == 1 and wl == "cfg3" and not shard and args.msckf_load_steps > 0:
+    if args.full and world == 1 and wl == "cfg3" and not shard and args.msckf_load_steps > 0:
         mgr.close()
         msckf_load = msckf_load_companion(U, args, dev)
     sharded = None
-    if world > 1 and not shard and args.sharded_steps > 0:
+    if args.full and world > 1 and not shard and args.sharded_steps > 0:
         mgr.close()
         frames = None
         sharded = sharded_companion(U, args, world, rank, dev, barrier)
@@ -636,7 +653,7 @@ def main():
             dom = max(cand, key=lambda k: cand[k]["device_s"]) if cand else None
             dom_by = {"source": "live HIP-event time of this run", "why": prof_why}
         cpu = None
-        if args.cpu_frames > 0:
+        if args.full and args.cpu_frames > 0:
             # the oracle needs only the clone window filled; fewer warm-up frames bound its run time
             cpu_warm = warm if images else min(warm, int(opts.max_clone_size) + 3)
             cpu = cpu_baseline(opts, wl, cpu_warm, args.cpu_frames, frames, sim_set)
@@ -697,6 +714,23 @@ def main():
     if world > 1:
         dist.destroy_process_group()
     return 0
+
+
+def dump_outputs(out_dir, mgr, rec, n_cams):
+    """--dump-outputs: what the caller of the timed path holds after its last step, one DIR/<name>.npy each (float64,
+    the tracks' pixels float32): the IMU state every timed step returned (imu_states, steps x 16; imu_state = the last
+    row), and the estimator's read-out after the last step -- state vector, covariance, and per camera the KLT
+    tracks (ids, uv) of image workloads.  A few MB at the largest workload (covariance <= ~700 x 700)."""
+    os.makedirs(out_dir, exist_ok=True)
+    xs = np.array([r[2] for r in rec], dtype=np.float64)
+    arrays = {"imu_states": xs, "imu_state": xs[-1], "state_vector": mgr.get_state_vector()[0],
+              "covariance": mgr.get_cov()}
+    for c in range(n_cams):
+        ids, uv = mgr.get_tracks(c)
+        arrays["tracks_cam%d_ids" % c] = ids.astype(np.float64)
+        arrays["tracks_cam%d_uv" % c] = uv.astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def msckf_load_companion(U, args, dev):

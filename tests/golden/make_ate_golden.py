@@ -1,8 +1,9 @@
 """Golden values for the ATE evaluator (uvio_amd/evaluation.py) on the reference's own ov_eval example pair:
 ov_eval/example/stamped_traj_estimate.txt (a VINS-Mono MH_01 run, ov_eval/example/readme.txt) against
 ov_data/euroc_mav/MH_01_easy.txt, the way `ov_eval error_singlerun posyaw` evaluates it
-(ResultTrajectory.cpp:26-109).  Only VALUES are committed (tests/golden/ate_ov_eval_example.json) -- the two
-trajectory files stay in /root/reference and are identified by their SHA-256.
+(ResultTrajectory.cpp:26-109).  The two trajectory files (data the reference's evaluator reads) are committed
+gzip-compressed next to this script (ov_eval_example_estimate.txt.gz, euroc_mh01_easy_groundtruth.txt.gz) and
+identified by the SHA-256 of their uncompressed bytes; unpack() writes them out as the text files the loader reads.
 
 Two independent computations:
   * uvio_amd.evaluation.ate_files: the restatement (association, yaw-only Umeyama through get_best_yaw,
@@ -10,26 +11,39 @@ Two independent computations:
   * procrustes_posyaw below: the same association, then the least-squares yaw / translation from an SVD of the
     2x2 horizontal cross-covariance (2-D Procrustes; z is untouched by a yaw), no shared code with the above.
 
-Run in this container (the reference is only here): python tests/golden/make_ate_golden.py
+Run: python tests/golden/make_ate_golden.py
 """
+import gzip
 import hashlib
 import json
 import os
 import sys
+import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
-REF = "/root/reference"
-EST = os.path.join(REF, "ov_eval", "example", "stamped_traj_estimate.txt")
-GT = os.path.join(REF, "ov_data", "euroc_mav", "MH_01_easy.txt")
+EST_GZ = os.path.join(HERE, "ov_eval_example_estimate.txt.gz")
+GT_GZ = os.path.join(HERE, "euroc_mh01_easy_groundtruth.txt.gz")
 OUT = os.path.join(ROOT, "tests", "golden", "ate_ov_eval_example.json")
 
 
 def sha256(path):
     with open(path, "rb") as f:
         return hashlib.sha256(f.read()).hexdigest()
+
+
+def unpack(out_dir):
+    """the two committed trajectories as text files in out_dir: (estimate path, ground-truth path)"""
+    paths = []
+    for gz, name in ((EST_GZ, "stamped_traj_estimate.txt"), (GT_GZ, "MH_01_easy.txt")):
+        p = os.path.join(str(out_dir), name)
+        with gzip.open(gz, "rb") as f, open(p, "wb") as g:
+            g.write(f.read())
+        paths.append(p)
+    return tuple(paths)
 
 
 def procrustes_posyaw(p_est, p_gt, q_est, q_gt):
@@ -67,7 +81,7 @@ def procrustes_posyaw(p_est, p_gt, q_est, q_gt):
     return {"pos_m": pos, "ori_deg": float(np.sqrt(np.mean(np.square(ang)))), "yaw_rad": yaw, "t": t.tolist()}
 
 
-def compute():
+def compute(EST, GT):
     from uvio_amd import evaluation as E
     r = E.ate_files(EST, GT)
     te, pe = E.load_traj(EST)
@@ -87,7 +101,8 @@ def compute():
 
 
 if __name__ == "__main__":
-    out = compute()
+    with tempfile.TemporaryDirectory() as tmp:
+        out = compute(*unpack(tmp))
     with open(OUT, "w") as f:
         json.dump(out, f, indent=1)
     print(json.dumps(out, indent=1))

@@ -4,8 +4,8 @@ TAG=${1:-ab}; PAIRS=${2:-3}; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG
 cd $R && mkdir -p $O
 for i in $(seq 1 $PAIRS); do
   for wl in ${WLS:-cfg3 cfg2}; do
-    timeout -k 10 200 python -u bench.py --workload $wl --steps 300 --cpu-frames 0 --no-host-feed > $O/new_${wl}_$i.json 2> /dev/null || exit 1
-    UVIO_HP_LIB=$R/build/abprev/libuvio_hp_prev.so UVIO_HP_AB_OLD=1 timeout -k 10 200 python -u bench.py --workload $wl --steps 300 --cpu-frames 0 --no-host-feed > $O/old_${wl}_$i.json 2> /dev/null || exit 1
+    timeout -k 10 200 python -u bench.py --full --workload $wl --steps 300 --cpu-frames 0 --no-host-feed > $O/new_${wl}_$i.json 2> /dev/null || exit 1
+    UVIO_HP_LIB=$R/build/abprev/libuvio_hp_prev.so UVIO_HP_AB_OLD=1 timeout -k 10 200 python -u bench.py --full --workload $wl --steps 300 --cpu-frames 0 --no-host-feed > $O/old_${wl}_$i.json 2> /dev/null || exit 1
   done
 done
 python - "$O" "${WLS:-cfg3 cfg2}" <<'PY'

@@ -8,5 +8,5 @@ cd $R && mkdir -p $O
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -v -s --timeout 300 --timeout-method thread > $O/gpu_tests.log 2>&1
 for ws in "$@"; do
   wl=${ws%%:*}; st=${ws##*:}
-  timeout -k 10 400 python -u bench.py --workload $wl --steps $st --cpu-frames 2 > $O/bench_$wl.json 2> $O/bench_$wl.err
+  timeout -k 10 400 python -u bench.py --full --workload $wl --steps $st --cpu-frames 2 > $O/bench_$wl.json 2> $O/bench_$wl.err
 done

@@ -25,13 +25,13 @@ if [ "$PART" = "1" ]; then
   timeout -k 10 900 python -u -m pytest tests -m gpu -x -v -s --timeout 300 --timeout-method thread > $O/gpu_tests.log 2>&1
   timeout -k 10 120 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 elif [ "$PART" = "2" ]; then
-  timeout -k 10 400 python -u bench.py > $O/${TAG}_cfg3_bench.json 2> $O/cfg3.err
-  timeout -k 10 400 python -u bench.py --workload cfg2 > $O/${TAG}_cfg2_bench.json 2> $O/cfg2.err
-  timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 > $O/${TAG}_cfg3_bench_driver_form.json 2> $O/cfg3_driver.err
-  timeout -k 10 300 python -u bench.py --steps 300 --cpu-frames 0 --msckf-load-steps 0 > $O/${TAG}_cfg3_bench_300.json 2> $O/cfg3_300.err
+  timeout -k 10 400 python -u bench.py --full > $O/${TAG}_cfg3_bench.json 2> $O/cfg3.err
+  timeout -k 10 400 python -u bench.py --full --workload cfg2 > $O/${TAG}_cfg2_bench.json 2> $O/cfg2.err
+  timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 > $O/${TAG}_cfg3_bench_driver_form.json 2> $O/cfg3_driver.err
+  timeout -k 10 300 python -u bench.py --full --steps 300 --cpu-frames 0 --msckf-load-steps 0 > $O/${TAG}_cfg3_bench_300.json 2> $O/cfg3_300.err
 else
   for wl in cfg3t cfg2l cfg4i cfg5i cfg5; do
-    timeout -k 10 400 python -u bench.py --workload $wl > $O/${TAG}_${wl}_bench.json 2> $O/$wl.err
+    timeout -k 10 400 python -u bench.py --full --workload $wl > $O/${TAG}_${wl}_bench.json 2> $O/$wl.err
   done
-  timeout -k 10 400 python -u bench.py --workload cfg4 --steps 300 > $O/${TAG}_cfg4_bench_300.json 2> $O/cfg4.err
+  timeout -k 10 400 python -u bench.py --full --workload cfg4 --steps 300 > $O/${TAG}_cfg4_bench_300.json 2> $O/cfg4.err
 fi

@@ -5,4 +5,4 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/$TAG
 cd $R && mkdir -p $O
 timeout -k 10 1000 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread "$@" > $O/gpu_tests.log 2>&1
-timeout -k 10 400 python -u bench.py > $O/bench_cfg2.json 2> $O/bench_cfg2.err
+timeout -k 10 400 python -u bench.py --full > $O/bench_cfg2.json 2> $O/bench_cfg2.err
