@@ -383,6 +383,11 @@ int uvio_hp_undistort(int model, const double cam[8], int n, const float *uv, fl
  * cell is arranged. */
 int uvio_hp_debug_grid_order(const uint8_t *resp, const int *off, int ncell, int kmax, int depth, int *arrangement,
                              int *top);
+/* histogram_method 2 (TrackKLT.cpp:56-67, cv::createCLAHE(10.0, Size(8, 8))->apply) as the tracker runs it, on a
+ * caller-given 8-bit image of any size w, h >= 9 (rows stride bytes apart): the tracker's own tile-LUT and level-0
+ * kernels on a one-level pyramid; out (w * h, packed) receives level 0.  UVIO_HP_E_ARG: null pointers, stride < w,
+ * a side below 9; UVIO_HP_E_CAPACITY: a side above 16384. */
+int uvio_hp_debug_clahe(const uint8_t *img, int w, int h, int stride, uint8_t *out);
 /* the tracker's FAST cells since the handle was created and how many of them had more than 16 candidates
  * (the cells where std::sort's introsort order, not a stable one, decides the selection) */
 int uvio_hp_debug_grid_stats(uvio_hp_t *h, uint64_t *cells, uint64_t *introsort_cells);

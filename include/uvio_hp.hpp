@@ -221,6 +221,15 @@ class Manager {
   }
 };
 
+// histogram_method CLAHE (cv::createCLAHE(10.0, Size(8, 8))->apply) of one 8-bit image with the tracker's own
+// kernels (uvio_hp_debug_clahe): w x h pixels, rows `stride` bytes apart, both sides >= 9; returns w * h packed
+inline std::vector<uint8_t> clahe(const uint8_t *img, int w, int h, int stride) {
+  std::vector<uint8_t> out(w > 0 && h > 0 ? (size_t)w * (size_t)h : 0);
+  const int rc = uvio_hp_debug_clahe(img, w, h, stride, out.data());
+  if (rc) throw Error(rc, "uvio_hp_debug_clahe");
+  return out;
+}
+
 }  // namespace uvio_amd
 
 #endif  // UVIO_HP_HPP

@@ -399,6 +399,16 @@ int uvio_hp_debug_grid_order(const uint8_t *resp, const int *off, int ncell, int
   }
 }
 
+int uvio_hp_debug_clahe(const uint8_t *img, int w, int h, int stride, uint8_t *out) {
+  try {
+    return Engine::clahe_standalone(img, w, h, stride, out);
+  } catch (const HpError &ex) {
+    return ex.code;
+  } catch (...) {
+    return UVIO_HP_E_DEVICE;
+  }
+}
+
 int uvio_hp_debug_grid_stats(uvio_hp_t *h, uint64_t *cells, uint64_t *introsort_cells) {
   if (!h) return UVIO_HP_E_ARG;
   unsigned long long c = 0;

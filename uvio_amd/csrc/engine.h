@@ -456,6 +456,7 @@ class Engine {
   static int undistort_standalone(int model, const double cam[8], int n, const float *uv, float *uvn, uint8_t *amb);
   static int grid_order_standalone(const uint8_t *resp, const int *off, int ncell, int kmax, int depth,
                                    int *arrangement, int *top);
+  static int clahe_standalone(const uint8_t *img, int w, int h, int stride, uint8_t *out);
 
  private:
   uvio_hp_options_t o_;

@@ -96,6 +96,8 @@ Engine::Engine(const uvio_hp_options_t &o, int device) : o_(o), device_(device) 
   // configurations the reference accepts but this build does not implement fail here, loudly
   if (!o_.use_klt) throw HpError(UVIO_HP_E_CONFIG, "use_klt: false (TrackDescriptor / ORB) is not implemented");
   if (o_.use_aruco) throw HpError(UVIO_HP_E_CONFIG, "use_aruco: true (TrackAruco) is not implemented");
+  if (o_.histogram_method < 0 || o_.histogram_method > 2)
+    throw HpError(UVIO_HP_E_CONFIG, "histogram_method: 0 (NONE), 1 (HISTOGRAM) or 2 (CLAHE)");
   if (o_.feat_rep_msckf != 0 && o_.feat_rep_msckf != 4)
     throw HpError(UVIO_HP_E_CONFIG, "feat_rep_msckf: only GLOBAL_3D / ANCHORED_MSCKF_INVERSE_DEPTH are implemented");
   if (o_.feat_rep_slam != 0 && o_.feat_rep_slam != 2 && o_.feat_rep_slam != 4)
@@ -467,7 +469,7 @@ void Engine::kernel_stats(bool flush, uvio_hp_kstat_t *out, int cap, int *n) {
        1},
       {"ldl", "k_ekf_fact", 1},
       {"lk", "k_lk", 0},
-      {"pyramid", "k_hist_multi,k_pyr_pair", 0},
+      {"pyramid", "k_hist_multi,k_clahe_lut,k_pyr_pair", 0},
       {"fast", "k_fast_score,k_fast_select", 0},
       {"subpix", "k_subpix", 0},
   };
@@ -1013,6 +1015,59 @@ int Engine::grid_order_standalone(const uint8_t *resp, const int *off, int ncell
   hipFree(d_arr);
   hipFree(d_top);
   hipStreamDestroy(s);
+  return 0;
+}
+
+namespace {
+// a standalone probe's stream and device buffers, released on every way out of its scope
+struct ProbeScope {
+  hipStream_t s = nullptr;
+  std::vector<void *> bufs;
+  ProbeScope() { HP_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
+  ProbeScope(const ProbeScope &) = delete;
+  ProbeScope &operator=(const ProbeScope &) = delete;
+  ~ProbeScope() {
+    if (s) (void)hipStreamSynchronize(s);  // nothing in flight on a buffer freed below
+    for (void *p : bufs) (void)hipFree(p);
+    if (s) (void)hipStreamDestroy(s);
+  }
+  template <class T>
+  T *alloc(size_t n) {
+    void *p = nullptr;
+    bufs.reserve(bufs.size() + 1);  // a failed push_back cannot strand the allocation
+    HP_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
+    bufs.push_back(p);
+    return (T *)p;
+  }
+};
+}  // namespace
+
+// histogram_method 2 on a caller-given image: the tracker's own launch_pyramids on a one-level pyramid
+int Engine::clahe_standalone(const uint8_t *img, int w, int h, int stride, uint8_t *out) {
+  if (!img || !out || w <= kClaheTiles || h <= kClaheTiles || stride < w) return UVIO_HP_E_ARG;
+  if (w > 16384 || h > 16384) return UVIO_HP_E_CAPACITY;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return UVIO_HP_E_DEVICE;
+  const size_t n = (size_t)w * h;
+  ProbeScope ps;
+  uint8_t *d_src = ps.alloc<uint8_t>(n), *d_img = ps.alloc<uint8_t>(n);
+  int16_t *d_der = ps.alloc<int16_t>(2 * n);
+  PyrJob job{};
+  job.ncam = 1;
+  job.method = 2;
+  job.p[0].levels = 1;
+  job.p[0].w[0] = w;
+  job.p[0].h[0] = h;
+  job.p[0].img[0] = d_img;
+  job.p[0].der[0] = d_der;
+  job.src[0] = d_src;
+  job.stride[0] = w;
+  job.clahe[0] = ps.alloc<uint8_t>(kClaheLutBytes);
+  HP_HIP(hipMemcpy2DAsync(d_src, w, img, stride, w, h, hipMemcpyHostToDevice, ps.s));
+  launch_pyramids(ps.s, job);
+  HP_HIP(hipGetLastError());
+  HP_HIP(hipMemcpyAsync(out, d_img, n, hipMemcpyDeviceToHost, ps.s));
+  HP_HIP(hipStreamSynchronize(ps.s));
   return 0;
 }
 

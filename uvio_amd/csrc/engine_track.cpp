@@ -215,6 +215,7 @@ Tracker::~Tracker() {
     if (kv.second.d_raw) (void)hipFree(kv.second.d_raw);
     if (kv.second.d_half) (void)hipFree(kv.second.d_half);
     if (kv.second.d_hist) (void)hipFree(kv.second.d_hist);
+    if (kv.second.d_clahe_lut) (void)hipFree(kv.second.d_clahe_lut);
     if (kv.second.d_score) (void)hipFree(kv.second.d_score);
   }
   if (d_lk_bytes_) (void)hipFree(d_lk_bytes_);
@@ -356,6 +357,8 @@ void Tracker::alloc_pyr(CamState &c, int w, int h) {
   if (downsample_) HP_HIP(hipMalloc(&c.d_half, (size_t)w * h));
   HP_HIP(hipMalloc(&c.d_hist, 256 * sizeof(unsigned)));
   HP_HIP(hipMemset(c.d_hist, 0, 256 * sizeof(unsigned)));  // cleared after use by each frame's pyramid
+  // CLAHE: the 64 tile LUTs, rebuilt by every frame's k_clahe_lut before level 0 reads them
+  if (histogram_method_ == 2) HP_HIP(hipMalloc(&c.d_clahe_lut, kClaheLutBytes));
   HP_HIP(hipMalloc(&c.d_score, (size_t)w * h));
 }
 
@@ -386,8 +389,6 @@ const std::vector<int> &Tracker::subsets(int count) {
 void Tracker::feed(double t, int ncam, const int *cam_ids, const uint8_t *const *imgs, const int *strides,
                    const uint8_t *const *masks, bool device_imgs, const DbSink &db,
                    std::function<void()> in_flight) {
-  if (histogram_method_ == 2)
-    throw HpError(UVIO_HP_E_CONFIG, "histogram_method 2 (CLAHE) is not implemented by the KLT front-end");
   if (ncam > kMaxCams) throw HpError(UVIO_HP_E_ARG, "too many cameras in one feed");
   // The predetection (worker thread, detection stream) reads only the last frame's pyramids, points, ids and masks.
   // When every camera of this feed already has its state (no insertion into cs_ while the worker reads it), this
@@ -404,7 +405,7 @@ void Tracker::feed(double t, int ncam, const int *cam_ids, const uint8_t *const 
   sync_wait = 0.0;
   PyrJob job{};
   job.ncam = ncam;
-  job.equalize = histogram_method_ == 1;
+  job.method = histogram_method_;
   DecimateJob dec{};
   dec.ncam = downsample_ ? ncam : 0;
   for (int k = 0; k < ncam; k++) {
@@ -435,6 +436,7 @@ void Tracker::feed(double t, int ncam, const int *cam_ids, const uint8_t *const 
     job.src[k] = src;
     job.stride[k] = stride;
     job.hist[k] = c.d_hist;
+    job.clahe[k] = c.d_clahe_lut;
     c.mask_new.clear();
     if (masks && masks[k]) {
       c.mask_new.resize((size_t)w * h);

@@ -317,18 +317,23 @@ struct DPyr {
   int w[kMaxPyrLevels], h[kMaxPyrLevels];
   int levels;
 };
-// one frame's cameras at once: equalizeHist (or copy) of src[c] (row stride stride[c]) into level 0 of
-// p[c], then every level's pyrDown + Scharr; hist[c]: 256 u32 scratch per camera
+// one frame's cameras at once: a copy (method 0), equalizeHist (1) or CLAHE (2; clipLimit 10, 8 x 8 tiles,
+// TrackKLT.cpp:56-67) of src[c] (row stride stride[c]) into level 0 of p[c], then every level's pyrDown +
+// Scharr; hist[c]: 256 u32 scratch per camera (method 1), clahe[c]: the camera's kClaheLutBytes tile LUTs
+// (method 2; every image side >= 9: the tile grid's extension reflects once)
+constexpr int kClaheTiles = 8, kClaheLutBytes = kClaheTiles * kClaheTiles * 256;
 struct PyrJob {
   DPyr p[kMaxCams];
   const uint8_t *src[kMaxCams];
   int stride[kMaxCams];
   unsigned *hist[kMaxCams];
-  int ncam, equalize;
+  uint8_t *clahe[kMaxCams];
+  int ncam, method;
 };
 void launch_pyramids(hipStream_t s, const PyrJob &job);
-// algorithmic bytes of launch_pyramids: histogram read, equalized level 0 + Scharr
-// written, every further level's source read, level and Scharr written
+// algorithmic bytes of launch_pyramids: histogram read (method 1) or tile-LUT pass (method 2:
+// the source read once more, the LUT table written and read), equalized level 0 + Scharr written, every
+// further level's source read, level and Scharr written
 double pyramid_bytes(const PyrJob &job);
 // downsample_cameras (VioManager.cpp:270-278): dst[c] (w x h) = pyrDown(src[c]) of the 2w x 2h input
 // (row stride stride[c]), BORDER_REFLECT_101, (sum + 128) >> 8, all cameras in one launch

@@ -34,8 +34,10 @@ __device__ __forceinline__ int reflect101(int p, int n) {
 
 // ---------------------------------------------------------------- fused multi-camera pyramid
 // All cameras of a frame in one launch per stage (blockIdx.z = camera), TWO pyramid levels per launch:
-//   k_hist_multi              histograms of the input images
-//   k_pyr_pair<true>  (l = 0) level 0 = LUT(src) (the LUT from the histogram scan) and level 1
+//   k_hist_multi              histograms of the input images (histogram_method 1)
+//   k_clahe_lut               the 8 x 8 tile LUTs of the input images (histogram_method 2)
+//   k_pyr_pair<true>  (l = 0) level 0 = LUT(src) (the LUT from the histogram scan; with CL the interpolation of
+//                             the tile LUTs) and level 1
 //   k_pyr_pair<false> (l = 2) level 2 = pyrDown(level 1) and level 3; (l = 4) level 4
 // A workgroup owns a 64 x 16 tile of level l and the 32 x 8 tile of level l+1 below it.  Level l is built in
 // LDS over the tile plus a 4-pixel margin (each cell the value at the reflect-101 coordinate, so the margin
@@ -98,31 +100,116 @@ __device__ __forceinline__ void write_level(const uint8_t *win, int x0, int y0, 
   }
 }
 
-template <bool EQ, int PW, int PH>
+// ---------------------------------------------------------------- CLAHE (histogram_method 2)
+// cv::createCLAHE(10.0, Size(8, 8))->apply() on CV_8UC1 (OpenCV 4.x clahe.cpp as DESIGN.md §4 restates it): 64
+// tile LUTs from clipped tile histograms of the image extended (reflect-101) to a multiple of 8 in both sides,
+// then every pixel interpolated between the LUTs of its four nearest tile centres.
+struct ClaheGeom {
+  int tw, th;  // tile size of the extended image
+};
+__device__ __forceinline__ ClaheGeom clahe_geom(int w, int h) {
+  const bool fit = w % kClaheTiles == 0 && h % kClaheTiles == 0;
+  // OpenCV's formula: once either side needs the extension, a side that divides gains a whole 8
+  const int ew = fit ? w : w + kClaheTiles - w % kClaheTiles, eh = fit ? h : h + kClaheTiles - h % kClaheTiles;
+  return {ew / kClaheTiles, eh / kClaheTiles};
+}
+// coordinate p along one axis: the two tile indices (clamped) and the weight of the second; the weight is
+// taken before the clamp, as CLAHE_Interpolation_Body does.  inv = 1.0f / tile size
+__device__ __forceinline__ void clahe_axis(int p, float inv, int &i1, int &i2, float &a) {
+  const float f = __fsub_rn(__fmul_rn((float)p, inv), 0.5f);
+  const int i = (int)floorf(f);
+  a = __fsub_rn(f, (float)i);
+  i1 = max(i, 0);
+  i2 = min(i + 1, kClaheTiles - 1);
+}
+
+// CLAHE_CalcLut_Body: one workgroup per tile and camera (blockIdx.x = tile, blockIdx.z = camera, blockDim ==
+// 256).  Histogram of the tile in LDS (the extension's pixels at their reflect-101 coordinates), clip at
+// max((int)(10.0 * area / 256), 1), the clipped mass spread as batch = clipped / 256 to every bin and the
+// residual one each to bins 0, step, 2 step, ... (closed form of the reference's loop), inclusive scan, then
+// lut = saturate(rint(cumsum * (255.0f / area))): integer work up to that one float product.
+__global__ void __launch_bounds__(256) k_clahe_lut(PyrJob job) {
+  __shared__ int hs[256];
+  __shared__ int clipped;
+  const int c = blockIdx.z, t = threadIdx.x;
+  const DPyr &p = job.p[c];
+  const int w = p.w[0], h = p.h[0], stride = job.stride[c];
+  const uint8_t *img = job.src[c];
+  const ClaheGeom g = clahe_geom(w, h);
+  const int area = g.tw * g.th;
+  const int x0 = (blockIdx.x % kClaheTiles) * g.tw, y0 = (blockIdx.x / kClaheTiles) * g.th;
+  hs[t] = 0;
+  if (t == 0) clipped = 0;
+  __syncthreads();
+  // eight byte loads issued before their counts (as k_hist_multi's unaligned path)
+  for (int e0 = t; e0 < area; e0 += 8 * 256) {
+    int v[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      const int e = min(e0 + 256 * k, area - 1), y = e / g.tw, x = e - y * g.tw;
+      v[k] = img[(size_t)reflect101(y0 + y, h) * stride + reflect101(x0 + x, w)];
+    }
+#pragma unroll
+    for (int k = 0; k < 8; k++)
+      if (e0 + 256 * k < area) atomicAdd(&hs[v[k]], 1);
+  }
+  __syncthreads();
+  const int clip = max((int)(10.0 * (double)area / 256.0), 1);
+  int hv = hs[t];
+  if (hv > clip) {
+    atomicAdd(&clipped, hv - clip);
+    hv = clip;
+  }
+  __syncthreads();
+  const int batch = clipped / 256, residual = clipped - 256 * batch;
+  hv += batch;
+  if (residual != 0) {
+    const int step = max(256 / residual, 1);
+    if (t % step == 0 && t / step < residual) hv++;
+  }
+  hs[t] = hv;
+  __syncthreads();
+  for (int o = 1; o < 256; o <<= 1) {
+    int v = (t >= o) ? hs[t - o] : 0;
+    __syncthreads();
+    hs[t] += v;
+    __syncthreads();
+  }
+  const float scale = __fdiv_rn(255.f, (float)area);
+  const int r = (int)rintf(__fmul_rn((float)hs[t], scale));
+  job.clahe[c][blockIdx.x * 256 + t] = (uint8_t)min(255, max(0, r));
+}
+
+// CL: level 0 = CLAHE(src) from the tile LUTs of k_clahe_lut (EQ launches only); the identity / equalizeHist
+// instantiation carries none of it
+template <bool EQ, int PW, int PH, bool CL = false>
 __global__ void __launch_bounds__(256) k_pyr_pair(PyrJob job, int l) {
+  static_assert(EQ || !CL, "CLAHE is a level-0 mode");
   using T = PairTile<PW, PH>;
-  __shared__ uint8_t lut[256];
-  __shared__ int scan[256];
+  __shared__ uint8_t lut[CL ? 1 : 256];
+  __shared__ int scan[CL ? 1 : 256];
   __shared__ int first;
   __shared__ uint8_t win[T::WH * T::WW];
   __shared__ uint8_t q[(T::QH + 2) * (T::QW + 2)];
   __shared__ uint8_t srcs[EQ ? 1 : T::SH * T::SW];
+  // the tile LUTs this window's pixels interpolate between (at most all 64; 3 x 3 of them at 752 x 480)
+  __shared__ uint32_t clut[CL ? kClaheLutBytes / 4 : 1];
   // tiles of one camera in raster order, a contiguous range of them per XCD (neighbouring tiles share their
   // margin rows / columns through that XCD's L2)
   const int idx = xcd_contiguous(blockIdx.x + blockIdx.z * gridDim.x, gridDim.x * gridDim.z);
   const int c = idx / gridDim.x, tile = idx - c * gridDim.x, t = threadIdx.x;
   // the levels 2-3 launch runs after level 0's has read the histogram: it clears it for the next frame (the
   // tracker zeroes it once at allocation), which saves a fill per camera and frame
-  if (!EQ && l == 2 && job.equalize && tile == 0) job.hist[c][t] = 0u;
+  if (!EQ && l == 2 && job.method == 1 && tile == 0) job.hist[c][t] = 0u;
   const DPyr &p = job.p[c];
   if (l >= p.levels) return;
   const int w = p.w[l], h = p.h[l];
   const int ntx = (w + PW - 1) / PW;
   const int x0 = (tile % ntx) * PW, y0 = (tile / ntx) * PH;
   if (y0 >= h) return;
-  if constexpr (EQ) {
+  if constexpr (EQ && !CL) {
     // LUT of EqualizeHistLut_Invoker from an inclusive LDS scan of the counts (blockDim == 256)
-    if (!job.equalize) {
+    if (!job.method) {
       lut[t] = (uint8_t)t;
     } else {
       const unsigned *hist = job.hist[c];
@@ -174,9 +261,53 @@ __global__ void __launch_bounds__(256) k_pyr_pair(PyrJob job, int l) {
         v[k] = src[(size_t)reflect101(by + wy, h) * sld + reflect101(bx + wx, w)];
       }
     }
+    if constexpr (CL) {
+      // The window's image coordinates after reflect-101 lie in [xlo, xhi] x [ylo, yhi] (a reflected margin
+      // cell falls inside the window's own range or the image's); the tile indices are monotone in the
+      // coordinate, so the LUTs (tx_lo .. tx_hi) x (ty_lo .. ty_hi) cover every cell.  Staged as 4-byte words.
+      const ClaheGeom g = clahe_geom(w, h);
+      const float inv_tw = __fdiv_rn(1.f, (float)g.tw), inv_th = __fdiv_rn(1.f, (float)g.th);
+      int tx_lo, tx_hi, ty_lo, ty_hi, unused;
+      float fa;
+      clahe_axis(max(bx, 0), inv_tw, tx_lo, unused, fa);
+      clahe_axis(min(bx + T::WW, w) - 1, inv_tw, unused, tx_hi, fa);
+      clahe_axis(max(by, 0), inv_th, ty_lo, unused, fa);
+      clahe_axis(min(by + T::WH, h) - 1, inv_th, unused, ty_hi, fa);
+      const int nlx = tx_hi - tx_lo + 1, nl = nlx * (ty_hi - ty_lo + 1);
+      const uint32_t *table = reinterpret_cast<const uint32_t *>(job.clahe[c]);
+      for (int e = t; e < nl * 64; e += 256) {
+        const int j = e >> 6, ly = j / nlx, lx = j - ly * nlx;
+        clut[e] = table[((ty_lo + ly) * kClaheTiles + tx_lo + lx) * 64 + (e & 63)];
+      }
+      __syncthreads();
+      const uint8_t *cl = reinterpret_cast<const uint8_t *>(clut);
 #pragma unroll
-    for (int k = 0; k < NWP; k++)
-      if (t + 256 * k < NW) win[t + 256 * k] = lut[v[k]];
+      for (int k = 0; k < NWP; k++) {
+        const int e = t + 256 * k;
+        if (e < NW) {
+          const int wy = e / T::WW, wx = e - wy * T::WW;
+          int tx1, tx2, ty1, ty2;
+          float xa, ya;
+          clahe_axis(reflect101(bx + wx, w), inv_tw, tx1, tx2, xa);
+          clahe_axis(reflect101(by + wy, h), inv_th, ty1, ty2, ya);
+          // a margin cell more than 3 past the image's edge can reflect out of the range above: nothing
+          // reads it (as in the pyrDown path below), its indices are clamped into the staged LUTs
+          const int c1 = min(max(tx1, tx_lo), tx_hi) - tx_lo, c2 = min(max(tx2, tx_lo), tx_hi) - tx_lo;
+          const int r1 = (min(max(ty1, ty_lo), ty_hi) - ty_lo) * nlx, r2 = (min(max(ty2, ty_lo), ty_hi) - ty_lo) * nlx;
+          const float xa1 = __fsub_rn(1.f, xa), ya1 = __fsub_rn(1.f, ya);
+          const float l11 = (float)cl[(r1 + c1) * 256 + v[k]], l12 = (float)cl[(r1 + c2) * 256 + v[k]];
+          const float l21 = (float)cl[(r2 + c1) * 256 + v[k]], l22 = (float)cl[(r2 + c2) * 256 + v[k]];
+          const float top = __fadd_rn(__fmul_rn(l11, xa1), __fmul_rn(l12, xa));
+          const float bot = __fadd_rn(__fmul_rn(l21, xa1), __fmul_rn(l22, xa));
+          const int r = (int)rintf(__fadd_rn(__fmul_rn(top, ya1), __fmul_rn(bot, ya)));
+          win[e] = (uint8_t)min(255, max(0, r));
+        }
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < NWP; k++)
+        if (t + 256 * k < NW) win[t + 256 * k] = lut[v[k]];
+    }
   } else {
     // level l-1 over every pyrDown tap of the window, at virtual coordinates (each cell the value at its
     // reflect-101 coordinate in level l-1).  Every window cell that is read later (rows / columns up to one
@@ -308,7 +439,8 @@ void launch_pyramids(hipStream_t s, const PyrJob &job) {
     auto [wl, hl] = tiles(l);
     return ((wl + pw - 1) / pw) * ((hl + ph - 1) / ph);
   };
-  if (job.equalize) {
+  if (job.method < 0 || job.method > 2) throw std::runtime_error("launch_pyramids: histogram method");
+  if (job.method == 1) {
     int w0 = 0, h0 = 0;
     for (int c = 0; c < job.ncam; c++) w0 = max(w0, job.p[c].w[0]), h0 = max(h0, job.p[c].h[0]);
     // the histograms are zero here: cleared by the previous frame's levels 2-3 launch (below), or at allocation
@@ -319,19 +451,29 @@ void launch_pyramids(hipStream_t s, const PyrJob &job) {
   }
   // level 0 (the big image): 64 x 16 tiles, four pixels per thread; levels >= 2 (<= 188 x 120 at 752 x 480):
   // 32 x 8 tiles, so each workgroup's serial staging and reduction stay short
-  hipLaunchKernelGGL((k_pyr_pair<true, 64, 16>), dim3(grid(0, 64, 16), 1, job.ncam), dim3(256), 0, s, job, 0);
+  if (job.method == 2) {
+    for (int c = 0; c < job.ncam; c++)
+      if (job.p[c].w[0] <= kClaheTiles || job.p[c].h[0] <= kClaheTiles || !job.clahe[c])
+        throw std::runtime_error("launch_pyramids: CLAHE needs image sides >= 9 and its LUT buffer");
+    hipLaunchKernelGGL(k_clahe_lut, dim3(kClaheTiles * kClaheTiles, 1, job.ncam), dim3(256), 0, s, job);
+    hipLaunchKernelGGL((k_pyr_pair<true, 64, 16, true>), dim3(grid(0, 64, 16), 1, job.ncam), dim3(256), 0, s, job, 0);
+  } else {
+    hipLaunchKernelGGL((k_pyr_pair<true, 64, 16>), dim3(grid(0, 64, 16), 1, job.ncam), dim3(256), 0, s, job, 0);
+  }
   for (int l = 2; l < maxl; l += 2)
     hipLaunchKernelGGL((k_pyr_pair<false, 32, 8>), dim3(grid(l, 32, 8), 1, job.ncam), dim3(256), 0, s, job, l);
 }
 
 double pyramid_bytes(const PyrJob &job) {
-  // histogram pass reads the input; every pair launch reads its source (the input, or level l-1) once and
-  // writes its two levels' images and derivatives
+  // histogram pass reads the input (CLAHE: the tile-LUT pass reads it, writes the LUT table, and level 0 reads
+  // the table); every pair launch reads its source (the input, or level l-1) once and writes its two levels'
+  // images and derivatives
   double b = 0.0;
   for (int c = 0; c < job.ncam; c++) {
     const DPyr &p = job.p[c];
     const double a0 = (double)p.w[0] * p.h[0];
-    b += (job.equalize ? a0 : 0.0) + a0;
+    b += (job.method ? a0 : 0.0) + a0;
+    if (job.method == 2) b += 2.0 * kClaheLutBytes;
     for (int l = 0; l < p.levels; l++) b += 5.0 * p.w[l] * p.h[l];
     for (int l = 2; l < p.levels; l += 2) b += (double)p.w[l - 1] * p.h[l - 1];
   }

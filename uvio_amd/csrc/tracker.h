@@ -84,6 +84,7 @@ class Tracker {
     uint8_t *d_raw = nullptr;  // staging of a host image (the raw 2w x 2h one with downsample_cameras)
     uint8_t *d_half = nullptr;  // downsample_cameras: the pyrDown'ed input (w x h)
     unsigned *d_hist = nullptr;
+    uint8_t *d_clahe_lut = nullptr;  // histogram_method 2: the 8 x 8 tile LUTs (kClaheLutBytes)
     uint8_t *d_score = nullptr;  // FAST score map (w x h)
     std::vector<uint8_t> mask_last, mask_new;  // host masks (empty = none)
     std::vector<KeyPt> pts_last;

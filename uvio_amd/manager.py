@@ -495,6 +495,23 @@ def grid_order(cells, kmax=0, depth=-1):
     return arrs, tops
 
 
+def clahe(img):
+    """histogram_method CLAHE (TrackKLT.cpp:56-67: cv::createCLAHE(10.0, Size(8, 8))->apply) of one 8-bit image
+    as the tracker runs it (uvio_hp_debug_clahe: its tile-LUT kernel and level-0 kernel); both sides >= 9."""
+    lib = N.load()
+    img = np.asarray(img)
+    if img.ndim != 2 or img.dtype != np.uint8:
+        raise ValueError("clahe: a 2-D uint8 image")
+    if img.strides[1] != 1 or img.strides[0] < img.shape[1]:
+        img = np.ascontiguousarray(img)
+    h, w = img.shape
+    out = np.zeros((h, w), dtype=np.uint8)
+    bp = C.POINTER(C.c_uint8)
+    rc = lib.uvio_hp_debug_clahe(img.ctypes.data_as(bp), w, h, img.strides[0], out.ctypes.data_as(bp))
+    N.check(rc, what="uvio_hp_debug_clahe")
+    return out
+
+
 def undistort(cam, uv, return_ambiguous=False):
     """CamBase::undistort_f (CamBase.h:89) of n pixel points on the device (uvio_hp_undistort); cam is a
     Camera of the options.  With return_ambiguous, also the per-point flags of the points the library
