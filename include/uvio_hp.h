@@ -147,10 +147,8 @@ typedef struct {
   int n_msckf, n_slam, n_slam_delayed, n_clones, cov_dim;
   int msckf_rows;   /* stacked rows m before compression */
   int msckf_cols;   /* H columns n */
-  /* device-side measurement of the per-feature linearize kernel over this frame (HIP events on the
-   * library's stream, recorded only while uvio_hp_set_kernel_timing has timing on; zero otherwise):
-   * launches, summed kernel seconds, and algorithmic FP64 FLOPs of those launches
-   * (3 Householder reflections 12*(2m_f)*(n_f+4) + chi2 2 r n^2 + 2 r^2 n + r^3/3 per feature) */
+  /* not filled (always zero): kept so the struct layout does not change.  The per-feature linearize kernel's
+   * launches, seconds and FLOPs are in the "feature" class of uvio_hp_get_kernel_stats */
   int k_feat_launches;
   double k_feat_s;
   double k_feat_flops;

@@ -159,6 +159,97 @@ def test_updater_level_rejects_unknown_slam_landmark(euroc_yaml):
     g.close()
 
 
+def test_updater_level_error_names_the_reference_routine(euroc_yaml):
+    """A failed updater-level call names the reference routine it stands for (UpdaterSLAM::delayed_init here), not
+    the device chain that runs it.  The error is an ordinary capacity refusal, raised before any device work:
+    200 candidates would need 600 more covariance columns than the state's capacity has."""
+    import uvio_amd as U
+    from uvio_amd.sim import SimStream
+    opts = U.load_options(euroc_yaml, max_msckf_in_update=60, max_slam_features=0)
+    sim = SimStream(opts, duration=8 / opts.track_frequency + 1.2, seed=3, spawn=30)
+    g = U.VioManager(opts)
+    sim.run(g, n_frames=6)
+    ct = g.get_clone_times()
+    N0 = g.cov_dim()
+    two = [(0, float(ct[-2]), 100.0, 100.0, 0.1, 0.1), (0, float(ct[-1]), 101.0, 100.0, 0.11, 0.1)]
+    with pytest.raises(RuntimeError, match=r"E_CAPACITY.*UpdaterSLAM::delayed_init"):
+        g.slam_delayed_init([(10 ** 9 + k, two) for k in range(200)])
+    assert g.cov_dim() == N0  # refused whole: nothing was initialized
+    with pytest.raises(RuntimeError, match=r"E_ARG.*UpdaterSLAM::update"):
+        g.slam_update([(987654321, two)])
+    g.close()
+
+
+def _snapshot_with_candidates(euroc_yaml, **kw):
+    """test_updater_level_calls_match_oracle's fixture: both managers in lock-step over 14 frames, the oracle
+    synced; returns them with the stream, the clone window's frame indices and the delayed-init candidates (long
+    tracks that continue into the next frame), all that are available."""
+    import uvio_amd as U
+    from oracle import oracle as O
+    from uvio_amd.sim import SimStream
+    opts = U.load_options(euroc_yaml, max_msckf_in_update=60, dt_slam_delay=100.0, **kw)
+    n = 14
+    sim = SimStream(opts, duration=(n + 6) / opts.track_frequency + 1.2, seed=11, spawn=40, frac_long=0.5)
+    g, o = U.VioManager(opts), O.OracleManager(opts)
+    sim.run([g, o], n_frames=n, before_frame=lambda nf, t: _sync(g, o))
+    _sync(g, o)
+    ct = g.get_clone_times()
+    assert len(ct) == opts.max_clone_size and np.allclose(ct, o.get_clone_times())
+    window = _frames_at(sim, ct)
+    tracks = _tracks(sim, opts, window)
+    nxt = set(int(f) for k in range(sim.K) for f in sim.frames[window[-1] + 1][k][0])
+    longf = sorted(f for f, m in tracks.items() if len(set(x[1] for x in m)) >= 6)
+    cands = [(f, tracks[f]) for f in longf if f in nxt]
+    return opts, sim, g, o, window, cands
+
+
+def test_delayed_init_beyond_the_configured_landmark_count(euroc_yaml):
+    """UpdaterSLAM::delayed_init takes whatever list it is given: 8 candidates with max_slam_features = 2.  The
+    update chain's regions used to be sized from max_slam_features (6 for this config); the covariance has room
+    for all 8 (its capacity includes spare clone and anchor columns), so the call must initialize them as the
+    oracle does."""
+    opts, sim, g, o, window, cands = _snapshot_with_candidates(euroc_yaml, max_slam_features=2, max_slam_in_update=10)
+    dset = cands[:8]
+    assert len(dset) == 8
+    N0 = g.cov_dim()
+    rg, ro = g.slam_delayed_init(dset), o.slam_delayed_init(dset)
+    assert _used(rg) == _used(ro)
+    used = sum(r["used"] for r in rg)
+    print("delayed init: %d of %d used, N %d -> %d" % (used, len(dset), N0, g.cov_dim()))
+    assert used >= 7
+    assert g.cov_dim() == N0 + 3 * used == o.get_cov().shape[0]
+    print("rel diff x %.2e P %.2e" % _same_state(g, o))
+    g.close()
+
+
+def test_slam_update_takes_its_list_as_one_batch(euroc_yaml):
+    """UpdaterSLAM::update linearizes its whole list at one state and applies one EKF update; the chunks of
+    max_slam_in_update are VioManager's.  With max_slam_in_update = 2 and 8 landmarks in one call, chunking
+    would differ from the oracle's single batch by 2e-5 in x and 6e-4 in P on this input."""
+    opts, sim, g, o, window, cands = _snapshot_with_candidates(euroc_yaml, max_slam_features=20, max_slam_in_update=2)
+    dset = cands[:8]
+    rg, ro = g.slam_delayed_init(dset), o.slam_delayed_init(dset)
+    assert _used(rg) == _used(ro)
+    _same_state(g, o)
+    _sync(g, o)
+    i_next = window[-1] + 1
+    t_last, t_next = float(g.get_clone_times()[-1]), float(sim.cam_t[i_next])
+    _feed_imu_until(sim, [g, o], t_last, t_next)
+    g.propagate_and_clone(t_next)
+    o.propagate_and_clone(t_next)
+    _same_state(g, o)
+    _sync(g, o)
+    tracks2 = _tracks(sim, opts, window + [i_next])
+    lms = [(f, tracks2[f]) for (f, _), r in zip(dset, rg) if r["used"]]
+    rg2, ro2 = g.slam_update(lms), o.slam_update(lms)
+    assert _used(rg2) == _used(ro2)
+    used = sum(r["used"] for r in rg2)
+    print("slam update: %d of %d landmarks used" % (used, len(lms)))
+    assert used >= 5  # more than two chunks' worth
+    print("rel diff x %.2e P %.2e" % _same_state(g, o))
+    g.close()
+
+
 def test_uwb_update_single_matches_oracle(euroc_yaml):
     """UpdaterUWB::update_single (UpdaterUWB.cpp:53-90) through the C ABI on a state snapshot, fixed and
     estimated anchors, one range consistent with the ground truth and one 20 m off (chi2-gated on both)."""

@@ -1,4 +1,4 @@
-# A/B of one environment switch on one box (e.g. UVIO_HP_NO_CHAIN=1), alternating runs so box drift hits both
+# A/B of one environment switch on one box (e.g. UVIO_HP_NO_PREDETECT=1), alternating runs so box drift hits both
 # arms alike.  usage: bash tools/gpu_env_ab.sh VAR=VALUE OUTDIR REPEATS STEPS workload...
 set -e
 R=$GRAFT_REPO_ROOT

@@ -328,11 +328,6 @@ struct DeviceBufs {
   int *iold = nullptr;
   // update batch
   int max_feat = 0, max_meas_total = 0, max_vars_total = 0, max_rows = 0, ldh = 0, max_ncol = 0;
-  DFeat *feats = nullptr;
-  DMeas *meas = nullptr;
-  DVar *vars = nullptr;
-  DClone *clones = nullptr;
-  DCam *cams = nullptr;
   DFeatOut *fout = nullptr;
   double *chi2 = nullptr;
   double *H = nullptr;       // H_all (max_rows x ldh)
@@ -341,22 +336,16 @@ struct DeviceBufs {
   size_t chi2S_cap = 0;      // doubles
   double *partials = nullptr;
   double *R = nullptr;       // compressed (ncol x ncol, + global Cholesky scratch)
-  int *hidx = nullptr;
   EkfScratch ekf{};
-  // pinned host staging
-  void *pin = nullptr;
-  size_t pin_bytes = 0;
+  // pinned mirrors of the results block (inside chain_host, below)
   double *dx_host = nullptr;
   int *neg_host = nullptr;
   DFeatOut *fout_host = nullptr;
-  double *aux_host = nullptr;  // 16 host-only landing slots (delayed-init residual, shard totals)
-  int fout_pending = 0;        // feature results not yet copied: they ride along with the next readback
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;  // feature-kernel timing
   // upload staging ring: small host tables of one launch group are packed into pinned memory and sent
   // with ONE copy (stage / stage_flush); the kernels read the device copy directly
   char *stg_h = nullptr, *stg_d = nullptr;
   size_t stg_cap = 0, stg_used = 0, stg_flushed = 0;
-  long long stg_epoch = 0;  // ring restarts so far (a reservation must not outlive one: run_batch checks)
+  long long stg_epoch = 0;  // ring restarts so far (a reservation must not outlive one: the chain checks)
   // [negative-diagonal count (8 B) | dx (cap + 15) | feature results (max features)], mirrored in pinned
   // memory at neg_host / dx_host / fout_host: an update's dx and its batch's results come back in ONE copy
   double *dxneg = nullptr;
@@ -381,10 +370,10 @@ struct DeviceBufs {
   std::vector<int> pre_hidx;  // columns of the pending prefactor (empty: none)
   int pre_N = -1;
   long long pre_epoch = -1;  // Engine::p_epoch_ when the prefactor was enqueued
-  // delayed-initialization chain (Engine::slam_delayed_init): per candidate one region of chain_stride doubles
-  // [dx (N) | chi2, accepted | init residual (3) | accepted, negative diagonals], chain_k candidates per chain,
-  // mirrored in pinned memory
-  // The frame chain's per-update regions sit right in front of dxneg (region r at dxneg - (r + 1) stride), and
+  // The update chain (Engine::update_frame): per update one region of chain_stride doubles; a delayed-initialization
+  // candidate's is [dx (N) | chi2, accepted | init residual (3) | accepted, negative diagonals].  chain_k regions,
+  // as many as the covariance has room for updates (alloc_device).
+  // The chain's per-update regions sit right in front of dxneg (region r at dxneg - (r + 1) stride), and
   // chain_host mirrors [regions | dx block | fout] in pinned memory, so the chain's regions and every batch's
   // per-feature results come back in ONE copy (chain_results_copy)
   double *chain = nullptr, *chain_host = nullptr;  // the allocations: [chain_k regions][dx block][fout]
@@ -561,7 +550,6 @@ class Engine {
     kprof_.on = ktime_period_ > 0 && frames_ % ktime_period_ == 0;
   }
   void shard_allreduce(double *dev, size_t count);
-  int msckf_update_sharded(std::vector<FeatP> &fv);
 
  public:
   struct FeatDebug {
@@ -621,17 +609,9 @@ class Engine {
       e->d_.pre_N = -1;
     }
   };
-  void ekf_update_info(int nch, int n, const std::vector<int> &hidx, double sigma2,
-                       const std::function<bool()> &apply = nullptr, const int *gate = nullptr,
-                       const double *partials = nullptr);
-  // hidx_dev: the batch's column map already on the device (staged), or nullptr to stage `hidx`;
-  // pre_apply runs after the readback, before dx is applied (initialize_invertible's landmark step)
-  // gate (device count, may be null): the P update is skipped on the device when it is 0; after the
-  // readback `apply` decides whether dx goes to the host mean (true when absent)
+  // a direct EKF update with its own readback (the zero-velocity update): dx goes to the host mean
   void ekf_update_rows(const double *Hdev, int ldh, int r, int n, const std::vector<int> &hidx, const double *resdev,
-                       int res_stride, double sigma2, const int *hidx_dev = nullptr,
-                       const std::function<bool()> &apply = nullptr, const int *gate = nullptr,
-                       const double *Tdev = nullptr);  // T = H P_II of these rows (ld ldh), if the chi2 gate left it
+                       int res_stride, double sigma2);
   void apply_dx(const double *dx);
   // staging (see DeviceBufs): returns the device address the table will have after stage_flush()
   void *stage_bytes(const void *src, size_t bytes);
@@ -683,7 +663,6 @@ class Engine {
   int after_tracking(double t, const std::vector<int> &camids, std::chrono::steady_clock::time_point rT1,
                      int track_syncs = 0, double track_wait = 0.0, bool try_init = false);
   int do_feature_propagate_update(double t, const std::vector<int> &camids, std::chrono::steady_clock::time_point rT2);
-  int msckf_update(std::vector<FeatP> &feats);
   void gram(int m, int ncol, int *nch);
   // VioManager::retriangulate_active_tracks on the device (engine_retri.cpp)
   struct RetriState {
@@ -713,8 +692,6 @@ class Engine {
   int get_active_tracks(double *t, uint64_t *ids, double *posinG, double *uvd, int *uvd_valid, int cap);
 
  private:
-  int slam_update(std::vector<FeatP> &feats);
-  int slam_delayed_init(std::vector<FeatP> &feats);
   int slam_change_anchors();
   int uwb_update_single(size_t anchor_id, double range);
   // UpdaterUWB::update_single for every range of one UwbData message whose anchor is known, in the message's
@@ -740,8 +717,7 @@ class Engine {
     std::vector<int> hidx;     // canonical column -> covariance id
     const int *hidx_dev = nullptr;  // its staged device copy
     bool finished = false;          // per-feature results read back (finish_batch)
-    bool evtimed = false;           // the feature group is bracketed by the ev0 / ev1 timing events
-    bool chi2 = true;               // the batch chi2 kernels ran (run_batch)
+    bool chi2 = true;               // the batch chi2 kernels ran
     std::vector<FeatP> fptrs;
     int n_canon = 0, rows = 0, max_meas = 0, max_nf = 0;
     // large batches write their measurement / variable tables straight into the upload staging
@@ -758,25 +734,20 @@ class Engine {
   void build_clone_cam_tables(Batch &b, bool include_landmarks);
   void add_feature_to_batch(Batch &b, const FeatP &f, int mode, int rep);
   void add_features_to_batch(Batch &b, const std::vector<FeatP> &fv, size_t lo, size_t hi, int mode, int rep);
-  // wait = false: only enqueue (kernels + result readback); the caller's next device sync completes it and
-  // finish_batch then fills outs
-  // chi2 = false: the feature kernel only (delayed init gates on its own update factor instead)
   DBatchParams batch_params(const Batch &b, double sigma_pix_sq, double chi2_mult) const;
-  // one chain of delayed initializations: fv[idx[0..]] (triangulated) linearized, initialized and updated on
-  // the device one after the other, one host wait at the end
-  int slam_delayed_chain(std::vector<FeatP> &fv, const std::vector<size_t> &idx, int rep, double s2);
-  // the frame's UpdaterMSCKF::update, UpdaterSLAM::update chunks and delayed_init as one device chain with one
-  // host wait (engine_chain.cpp)
-  int update_frame(std::vector<FeatP> &msckf, std::vector<FeatP> &slam_upd, std::vector<FeatP> &delayed);
+  // UpdaterMSCKF::update, UpdaterSLAM::update in chunks of slam_chunk features and UpdaterSLAM::delayed_init as
+  // one device chain with one host wait (engine_chain.cpp): the frame's three lists, or one updater-level call's
+  // list with the other two empty.  `stage` is what stage() names while it runs.
+  int update_frame(std::vector<FeatP> &msckf, std::vector<FeatP> &slam_upd, std::vector<FeatP> &delayed,
+                   size_t slam_chunk, const char *stage = "update chain");
   struct ChainItem;
+  // the chain's replay on the host mean, per kind of item, after the one readback
+  void replay_msckf(ChainItem &it);
+  void replay_slam(ChainItem &it);
+  void replay_delayed(ChainItem &tri, ChainItem &cand, int N0);
   double chain_times_[3] = {0, 0, 0};  // host seconds of the chain's MSCKF / SLAM / delayed-init parts
-  // UVIO_HP_NO_CHAIN set when the engine is created: the updaters one after the other with their host waits
-  // (A/B runs and diagnostics)
-  const bool no_chain_ = std::getenv("UVIO_HP_NO_CHAIN") != nullptr;
   // 3-wide variables (zeroed landmark slots) at the given covariance offsets leave P in one compaction
   void marginalize_slots(std::vector<int> slots);
-  int run_batch(Batch &b, int mode, double sigma_pix_sq, double chi2_mult, bool wait, std::vector<DFeatOut> &outs,
-                bool chi2 = true);
   void finish_batch(Batch &b, int mode, std::vector<DFeatOut> &outs);
 };
 

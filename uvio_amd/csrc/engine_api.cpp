@@ -61,19 +61,27 @@ int Engine::api_update(int which, int nfeat, const uint64_t *featids, const int 
                        const uvio_hp_feat_meas_t *meas, uvio_hp_feat_result_t *out) {
   if (!is_initialized_) throw HpError(UVIO_HP_E_STATE, "updater call before initialization");
   if (nfeat < 0 || (nfeat > 0 && (!featids || !meas_off || !meas || !out))) return UVIO_HP_E_ARG;
-  std::vector<FeatP> fv = make_features(nfeat, featids, meas_off, meas, o_.num_cameras);
-  const std::vector<FeatP> in = fv;
+  static const char *const routine[3] = {"UpdaterMSCKF::update", "UpdaterSLAM::update", "UpdaterSLAM::delayed_init"};
+  if (which < API_MSCKF || which > API_DELAYED) return UVIO_HP_E_ARG;
+  stage_ = routine[which];
+  const std::vector<FeatP> in = make_features(nfeat, featids, meas_off, meas, o_.num_cameras);
   if (which == API_SLAM)
-    for (auto &f : fv)
+    for (auto &f : in)
       if (slam_.find(f->featid) == slam_.end()) throw HpError(UVIO_HP_E_ARG, "UpdaterSLAM::update: feature is not a SLAM landmark");
+  // The one implementation of the three updaters is the frame's chain (engine_chain.cpp): the caller's list goes
+  // into its slot, the other two stay empty.  UpdaterSLAM::update takes its whole list as one batch (the chunks of
+  // max_slam_in_update are VioManager's), so the list is a single chunk here.  The chain's other side effects are
+  // harmless from this call: it flushes a pending retriangulation (the job was taken at its frame; only the
+  // active-track output depends on it) and refills the feature stock (an allocation cache), and chain_times_ /
+  // timing_.chain_wait are timing read-outs.  Its errors name the reference routine, as stage() does.
+  std::vector<FeatP> lists[3];
+  lists[which] = in;
   int rc = 0;
-  last_upd_.clear();
-  if (which == API_MSCKF)
-    rc = msckf_update(fv);
-  else if (which == API_SLAM)
-    rc = slam_update(fv);
-  else
-    rc = slam_delayed_init(fv);
+  try {
+    rc = update_frame(lists[API_MSCKF], lists[API_SLAM], lists[API_DELAYED], in.size(), routine[which]);
+  } catch (const HpError &ex) {
+    throw HpError(ex.code, std::string(routine[which]) + ": " + ex.what());
+  }
   if (rc) return rc;
   const std::vector<FeatDebug> &res = (which == API_MSCKF) ? last_msckf_ : last_upd_;
   std::unordered_map<size_t, const FeatDebug *> by_id;

@@ -75,15 +75,17 @@ struct Engine::ChainItem {
   const int *t_hidx = nullptr;
 };
 
-int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, std::vector<FeatP> &delayed) {
-  stage_ = "update chain";
+int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, std::vector<FeatP> &delayed,
+                         size_t slam_chunk, const char *stage_name) {
+  stage_ = stage_name;
   last_msckf_.clear();
   last_upd_.clear();
   std::vector<double> clonetimes;
   for (auto &c : clones_) clonetimes.push_back(c.first);
   // ---- 0) each updater's measurement cleaning (UpdaterMSCKF.cpp:69-86, UpdaterSLAM.cpp:68-84 / 262-283);
   // the clone set does not change during the updates, so all three lists are cleaned up front.  The SLAM
-  // list is split into its max_slam_in_update chunks first (VioManager.cpp:533-545) and each chunk is
+  // list is split into its chunks of slam_chunk features first (one UpdaterSLAM::update call each: the frame's
+  // max_slam_in_update, VioManager.cpp:533-545, or the whole list of an updater-level call) and each chunk is
   // cleaned on its own, as UpdaterSLAM::update does: a feature left without measurements shrinks its chunk,
   // it does not pull the next chunk's features forward
   {
@@ -106,7 +108,7 @@ int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, s
   }
   std::vector<std::vector<FeatP>> slam_chunks;
   {
-    const size_t chunk = (size_t)std::max(o_.max_slam_in_update, 1);
+    const size_t chunk = std::max(slam_chunk, (size_t)1);
     std::vector<FeatP> all;
     for (size_t c0 = 0; c0 < slam_upd.size(); c0 += chunk) {
       std::vector<FeatP> keep;
@@ -229,8 +231,8 @@ int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, s
     it->kind = 0;
     size_t lo = 0, hi = up.size();
     if (shard_.enabled && (int)up.size() >= shard_.min_features) {
-      // UpdaterMSCKF::update split across the ranks inside the chain (shard.cpp: the same partition, pack and
-      // all-reduce as msckf_update_sharded; over RCCL the all-reduce is enqueued on the chain's stream)
+      // UpdaterMSCKF::update split across the ranks inside the chain (shard.cpp: the partition and the
+      // all-reduce; over RCCL the all-reduce is enqueued on the chain's stream)
       std::vector<int> rows(up.size()), bounds(shard_.world + 1);
       for (size_t i = 0; i < up.size(); i++) rows[i] = 2 * up[i]->count() - 3;
       shard_partition(rows.data(), (int)up.size(), shard_.world, bounds.data());
@@ -277,7 +279,6 @@ int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, s
   double *fr_xv = (double *)(frame + o_xv);
 
   int fo = 0, nreg = 0;
-  const size_t st = d_.chain_stride;
   auto new_region = [&]() {
     if (nreg >= d_.chain_k) throw HpError(UVIO_HP_E_CAPACITY, "update chain: too many updates in one frame");
     return nreg++;
@@ -342,6 +343,35 @@ int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, s
     }
     it.m = b.rows;
   };
+  // after an update: P has changed, and the state tables move by the update's dx when it was accepted
+  auto enqueue_apply = [&](const EkfScratch &sc) {
+    ++p_epoch_;
+    launch_chain_apply(d_.stream, nullptr, d_.acc, sc.neg, sc.dx, fr_cl, fr_cv, ncl, fr_cam, fr_camv, ncam,
+                       o_.do_calib_camera_pose, o_.do_calib_camera_intrinsics, fr_xv, N_, d_.P, d_.ldp, N_, -1,
+                       sc.dx + N_ + 8);
+  };
+  // the information-form update on the Gram G (nch partial chunks) of a batch's stacked rows, with the side-stream
+  // prefactor of its columns when that is in flight and P is unchanged since it was enqueued; then the apply step
+  auto enqueue_info_update = [&](const Batch &b, const double *G, int nch, double s2, EkfScratch &sc) {
+    const int n = b.n_canon;
+    const bool inflight = d_.pre_N >= 0;
+    const bool pre = inflight && d_.pre_N == N_ && d_.pre_hidx == b.hidx && d_.pre_epoch == p_epoch_;
+    d_.pre_hidx.clear();
+    d_.pre_N = -1;
+    // (a stale prefactor still writes the factor scratch on the side stream: the full update waits for it too)
+    if (inflight) HP_HIP(hipStreamWaitEvent(d_.stream, d_.ev_aux_out, 0));
+    {
+      KScope ks(&kprof_, KC_EKF);
+      if (pre)
+        launch_ekf_info_post(d_.stream, d_.P, d_.ldp, N_, G, nch, n, s2, d_.R, sc);
+      else
+        launch_ekf_info(d_.stream, d_.P, d_.ldp, N_, G, nch, n, b.hidx_dev, s2, d_.R, sc);
+    }
+    // the timed launches: without the prefactor (Cholesky of P_II, n^3 / 3, and V, N n^2) when it ran
+    const double fl = ekf_flops(N_, n, n) - (pre ? (double)n * n * n / 3.0 + (double)N_ * n * n : 0.0);
+    kprof_.credit(KC_EKF, fl, ekf_bytes(N_, n, n));
+    enqueue_apply(sc);
+  };
   // the EKF update of a batch's stacked rows (direct, or information form on their Gram), gated by the batch's
   // accepted count, dx into a fresh region; then the state tables move by it
   auto enqueue_update = [&](ChainItem &it, double s2) {
@@ -354,32 +384,17 @@ int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, s
     if (m > n || m > kMaxEkfRows) {
       int nch = 0;
       gram(m, ncol, &nch);
-      const bool inflight = d_.pre_N >= 0;
-      const bool pre = inflight && d_.pre_N == N_ && d_.pre_hidx == b.hidx && d_.pre_epoch == p_epoch_;
-      d_.pre_hidx.clear();
-      d_.pre_N = -1;
-      if (pre) {
-        HP_HIP(hipStreamWaitEvent(d_.stream, d_.ev_aux_out, 0));
-        KScope ks(&kprof_, KC_EKF);
-        launch_ekf_info_post(d_.stream, d_.P, d_.ldp, N_, d_.partials, nch, n, s2, d_.R, sc);
-      } else {
-        if (inflight) HP_HIP(hipStreamWaitEvent(d_.stream, d_.ev_aux_out, 0));
-        KScope ks(&kprof_, KC_EKF);
-        launch_ekf_info(d_.stream, d_.P, d_.ldp, N_, d_.partials, nch, n, b.hidx_dev, s2, d_.R, sc);
-      }
-      const double fl = ekf_flops(N_, n, n) - (pre ? (double)n * n * n / 3.0 + (double)N_ * n * n : 0.0);
-      kprof_.credit(KC_EKF, fl, ekf_bytes(N_, n, n));
-    } else {
-      sc.Tall = d_.Tall;
-      sc.ldt = d_.ldh;
+      enqueue_info_update(b, d_.partials, nch, s2, sc);
+      return;
+    }
+    sc.Tall = d_.Tall;
+    sc.ldt = d_.ldh;
+    {
       KScope ks(&kprof_, KC_EKF);
       launch_ekf_update(d_.stream, d_.P, d_.ldp, N_, d_.H, d_.ldh, m, n, b.hidx_dev, d_.H + n, d_.ldh, s2, sc);
-      kprof_.credit(KC_EKF, ekf_flops(N_, n, m), ekf_bytes(N_, n, m));
     }
-    ++p_epoch_;
-    launch_chain_apply(d_.stream, nullptr, d_.acc, sc.neg, sc.dx, fr_cl, fr_cv, ncl, fr_cam, fr_camv, ncam,
-                       o_.do_calib_camera_pose, o_.do_calib_camera_intrinsics, fr_xv, N_, d_.P, d_.ldp, N_, -1,
-                       sc.dx + N_ + 8);
+    kprof_.credit(KC_EKF, ekf_flops(N_, n, m), ekf_bytes(N_, n, m));
+    enqueue_apply(sc);
   };
 
   // the sharded MSCKF update: this rank's Gram packed with its accepted count and rows, all-reduced over the ranks
@@ -387,7 +402,7 @@ int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, s
   // Gram on every rank; the totals [accepted, rows] go to the region (N + 10, N + 11) for the replay
   auto enqueue_sharded_update = [&](ChainItem &it, double s2) {
     Batch &b = it.b;
-    const int m = b.rows, n = b.n_canon, ncol = n + 1;
+    const int m = b.rows, ncol = b.n_canon + 1;
     it.region = new_region();
     EkfScratch sc = d_.ekf;
     sc.dx = region(it.region);
@@ -399,25 +414,7 @@ int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, s
     launch_shard_unpack(d_.stream, d_.shard, ncol, d_.acc);
     HP_HIP(hipMemcpyAsync(sc.dx + N_ + 10, d_.shard + (size_t)ncol * ncol, 2 * sizeof(double), hipMemcpyDeviceToDevice,
                           d_.stream));
-    const bool inflight = d_.pre_N >= 0;
-    const bool pre = inflight && d_.pre_N == N_ && d_.pre_hidx == b.hidx && d_.pre_epoch == p_epoch_;
-    d_.pre_hidx.clear();
-    d_.pre_N = -1;
-    if (pre) {
-      HP_HIP(hipStreamWaitEvent(d_.stream, d_.ev_aux_out, 0));
-      KScope ks(&kprof_, KC_EKF);
-      launch_ekf_info_post(d_.stream, d_.P, d_.ldp, N_, d_.shard, 1, n, s2, d_.R, sc);
-    } else {
-      if (inflight) HP_HIP(hipStreamWaitEvent(d_.stream, d_.ev_aux_out, 0));
-      KScope ks(&kprof_, KC_EKF);
-      launch_ekf_info(d_.stream, d_.P, d_.ldp, N_, d_.shard, 1, n, b.hidx_dev, s2, d_.R, sc);
-    }
-    kprof_.credit(KC_EKF, ekf_flops(N_, n, n) - (pre ? (double)n * n * n / 3.0 + (double)N_ * n * n : 0.0),
-                  ekf_bytes(N_, n, n));
-    ++p_epoch_;
-    launch_chain_apply(d_.stream, nullptr, d_.acc, sc.neg, sc.dx, fr_cl, fr_cv, ncl, fr_cam, fr_camv, ncam,
-                       o_.do_calib_camera_pose, o_.do_calib_camera_intrinsics, fr_xv, N_, d_.P, d_.ldp, N_, -1,
-                       sc.dx + N_ + 8);
+    enqueue_info_update(b, d_.shard, 1, s2, sc);
   };
 
   // ---- 3) UpdaterMSCKF::update
@@ -599,7 +596,6 @@ int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, s
   {
     HPROF("chain.wait");
     chain_results_copy(nreg, fo);
-    d_.fout_pending = 0;
     // the next frame's detection (Tracker::predetect) while the device runs this chain: it reads only this
     // frame's tracker results; on the tracker's detection stream and worker thread, joined by the next feed
     if (camera_frame_ && predetect_on_ && tracker_) {
@@ -623,107 +619,15 @@ int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, s
     }
     dev_sync();
   }
-  auto tm3 = clk::now();
   // ---- 6) replay on the host mean, in the reference's order
   HPROF("chain.replay");
-  auto neg_check = [&](const double *base, int N) {
-    if (base[N + 9] > 0.5) throw HpError(UVIO_HP_E_NUMERIC, "EKFUpdate: negative covariance diagonal");
-  };
-  std::vector<DFeatOut> outs;
   for (auto &itp : items) {
-    ChainItem &it = *itp;
-    if (it.kind == 0) {
-      finish_batch(it.b, 0, outs);
-      for (auto &f : it.fv_all) f->to_delete = true;  // sharded: every rank's features leave the database
-      int acc = 0, acc_rows = 0;
-      for (size_t i = 0; i < outs.size(); i++) {
-        last_msckf_.push_back(FeatDebug{it.fv[i]->featid, {outs[i].p_FinG[0], outs[i].p_FinG[1], outs[i].p_FinG[2]},
-                                        outs[i].status == 2 ? 1 : outs[i].status, outs[i].chi2});
-        frame_feats_.push_back({0, last_msckf_.back()});
-        it.fv[i]->to_delete = true;
-        for (int k = 0; k < 3; k++) it.fv[i]->p_FinG[k] = outs[i].p_FinG[k], it.fv[i]->p_FinA[k] = outs[i].p_FinA[k];
-        if (outs[i].status == 0) acc++, acc_rows += outs[i].rows;
-      }
-      timing_.msckf_rows = acc_rows;
-      timing_.msckf_cols = it.b.n_canon;
-      if (it.region >= 0) {
-        const double *base = d_.region_host(it.region);
-        neg_check(base, N_);
-        if (it.sharded) {  // the update's acceptance and rows are every rank's (the all-reduced totals)
-          acc = base[N_ + 8] > 0.5 ? 1 : 0;
-          timing_.msckf_rows = (int)(base[N_ + 11] + 0.5);
-        }
-        if (acc > 0) apply_dx(base);
-      }
-    } else if (it.kind == 1) {
-      finish_batch(it.b, 1, outs);
-      last_upd_.clear();
-      int acc = 0;
-      for (size_t i = 0; i < outs.size(); i++) {
-        last_upd_.push_back(FeatDebug{it.fv[i]->featid, {0.0, 0.0, 0.0}, outs[i].status == 2 ? 1 : outs[i].status, outs[i].chi2});
-        frame_feats_.push_back({1, last_upd_.back()});
-        it.fv[i]->to_delete = true;
-        if (outs[i].status == 3) slam_.at(it.fv[i]->featid)->fail_count++;
-        if (outs[i].status == 0) acc++;
-      }
-      if (it.region >= 0) {
-        const double *base = d_.region_host(it.region);
-        neg_check(base, N_);
-        if (acc > 0) apply_dx(base);
-      }
-    } else if (it.kind == 3) {
-      std::vector<DFeatOut> touts;
-      finish_batch(tri->b, 2, touts);
-      finish_batch(it.b, 3, outs);
-      last_upd_.clear();
-      N_ = N0 + 3 * K;
-      std::vector<int> dead;
-      for (int j = 0; j < K; j++) {
-        FeatP &f = it.fv[j];
-        const int Ni = N0 + 3 * j, nup = 2 * it.b.feats[j].nmeas - 3;
-        f->to_delete = true;
-        if (touts[j].status == 1 || touts[j].status == 2) {
-          last_upd_.push_back(FeatDebug{f->featid, {0.0, 0.0, 0.0}, touts[j].status, 0.0});
-          frame_feats_.push_back({2, FeatDebug{f->featid, {0.0, 0.0, 0.0}, 1, 0.0}});
-          dead.push_back(Ni);
-          continue;
-        }
-        // anchor (host rule, identical to the kernel's) and the triangulated position
-        f->anchor_cam_id = it.b.feats[j].anchor_cam;
-        f->anchor_clone_timestamp = f->find((size_t)f->anchor_cam_id)->m.back().t;
-        for (int k = 0; k < 3; k++) f->p_FinA[k] = touts[j].p_FinA[k], f->p_FinG[k] = touts[j].p_FinG[k];
-        const double *base = d_.region_host(it.region + j);
-        if (base[Ni + 9] > 0.5) throw HpError(UVIO_HP_E_NUMERIC, "EKFUpdate: negative covariance diagonal");
-        const bool accepted = base[Ni + 8] > 0.5;
-        last_upd_.push_back(FeatDebug{f->featid, {f->p_FinG[0], f->p_FinG[1], f->p_FinG[2]}, accepted ? 0 : 3,
-                                      nup > 0 ? base[Ni + 3] : 0.0});
-        frame_feats_.push_back({2, last_upd_.back()});
-        if (!accepted) {
-          dead.push_back(Ni);
-          continue;
-        }
-        VarP lm = std::make_shared<Var>(V_LANDMARK, 3, 3);
-        lm->featid = f->featid;
-        lm->rep = rep_slam;
-        lm->unique_cam = f->anchor_cam_id;
-        lm->anchor_cam = f->anchor_cam_id;
-        lm->anchor_time = f->anchor_clone_timestamp;
-        const bool relr = (rep_slam == 2 || rep_slam == 4);
-        lm->set_xyz(relr ? f->p_FinA : f->p_FinG, false);
-        lm->set_xyz(relr ? f->p_FinA : f->p_FinG, true);
-        lm->id = Ni;
-        vars_.push_back(lm);
-        double HLinv[9], dl[3];
-        inv3_cofactor(outs[j].HfR, HLinv);  // the device's formula: identical H_Linv
-        const double *resinit = base + Ni + 5;
-        for (int a = 0; a < 3; a++)
-          dl[a] = HLinv[3 * a] * resinit[0] + HLinv[3 * a + 1] * resinit[1] + HLinv[3 * a + 2] * resinit[2];
-        lm->update(dl);
-        if (nup > 0) apply_dx(base);
-        slam_.insert({f->featid, lm});
-      }
-      marginalize_slots(dead);  // the rejected candidates' zeroed slots
-    }
+    if (itp->kind == 0)
+      replay_msckf(*itp);
+    else if (itp->kind == 1)
+      replay_slam(*itp);
+    else if (itp->kind == 3)
+      replay_delayed(*tri, *itp, N0);
   }
   auto tm4 = clk::now();
   // each updater's host time: its tables + its launches; the one wait and the replay go with the last
@@ -731,8 +635,116 @@ int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, s
   chain_times_[1] = t_build[1] + t_launch[1];
   chain_times_[2] = t_build[2] + t_launch[2] + secs(tw, tm4);
   timing_.chain_wait = secs(tw, tm4);
-  (void)tm3;
   return 0;
+}
+
+// ---- the chain's replay on the host mean, one function per kind of item (called in the reference's order) ----
+
+static void neg_check(const double *base, int N) {
+  if (base[N + 9] > 0.5) throw HpError(UVIO_HP_E_NUMERIC, "EKFUpdate: negative covariance diagonal");
+}
+
+// UpdaterMSCKF::update: per-feature results, then the update's dx
+void Engine::replay_msckf(ChainItem &it) {
+  std::vector<DFeatOut> outs;
+  finish_batch(it.b, 0, outs);
+  for (auto &f : it.fv_all) f->to_delete = true;  // sharded: every rank's features leave the database
+  int acc = 0, acc_rows = 0;
+  for (size_t i = 0; i < outs.size(); i++) {
+    last_msckf_.push_back(FeatDebug{it.fv[i]->featid, {outs[i].p_FinG[0], outs[i].p_FinG[1], outs[i].p_FinG[2]},
+                                    outs[i].status == 2 ? 1 : outs[i].status, outs[i].chi2});
+    frame_feats_.push_back({0, last_msckf_.back()});
+    it.fv[i]->to_delete = true;
+    for (int k = 0; k < 3; k++) it.fv[i]->p_FinG[k] = outs[i].p_FinG[k], it.fv[i]->p_FinA[k] = outs[i].p_FinA[k];
+    if (outs[i].status == 0) acc++, acc_rows += outs[i].rows;
+  }
+  timing_.msckf_rows = acc_rows;
+  timing_.msckf_cols = it.b.n_canon;
+  if (it.region < 0) return;
+  const double *base = d_.region_host(it.region);
+  neg_check(base, N_);
+  if (it.sharded) {  // the update's acceptance and rows are every rank's (the all-reduced totals)
+    acc = base[N_ + 8] > 0.5 ? 1 : 0;
+    timing_.msckf_rows = (int)(base[N_ + 11] + 0.5);
+  }
+  if (acc > 0) apply_dx(base);
+}
+
+// one UpdaterSLAM::update chunk
+void Engine::replay_slam(ChainItem &it) {
+  std::vector<DFeatOut> outs;
+  finish_batch(it.b, 1, outs);
+  last_upd_.clear();
+  int acc = 0;
+  for (size_t i = 0; i < outs.size(); i++) {
+    last_upd_.push_back(FeatDebug{it.fv[i]->featid, {0.0, 0.0, 0.0}, outs[i].status == 2 ? 1 : outs[i].status, outs[i].chi2});
+    frame_feats_.push_back({1, last_upd_.back()});
+    it.fv[i]->to_delete = true;
+    if (outs[i].status == 3) slam_.at(it.fv[i]->featid)->fail_count++;
+    if (outs[i].status == 0) acc++;
+  }
+  if (it.region < 0) return;
+  const double *base = d_.region_host(it.region);
+  neg_check(base, N_);
+  if (acc > 0) apply_dx(base);
+}
+
+// UpdaterSLAM::delayed_init: the batch triangulation's results (tri), then candidate by candidate (cand; slot
+// N0 + 3 j, region cand.region + j) the new landmark and its update's dx; the rejected candidates' zeroed slots
+// leave the covariance in one compaction
+void Engine::replay_delayed(ChainItem &tri, ChainItem &cand, int N0) {
+  const int K = (int)cand.fv.size(), rep_slam = o_.feat_rep_slam;
+  std::vector<DFeatOut> touts, outs;
+  finish_batch(tri.b, 2, touts);
+  finish_batch(cand.b, 3, outs);
+  last_upd_.clear();
+  N_ = N0 + 3 * K;
+  std::vector<int> dead;
+  for (int j = 0; j < K; j++) {
+    FeatP &f = cand.fv[j];
+    const int Ni = N0 + 3 * j, nup = 2 * cand.b.feats[j].nmeas - 3;
+    f->to_delete = true;
+    if (touts[j].status == 1 || touts[j].status == 2) {
+      last_upd_.push_back(FeatDebug{f->featid, {0.0, 0.0, 0.0}, touts[j].status, 0.0});
+      frame_feats_.push_back({2, FeatDebug{f->featid, {0.0, 0.0, 0.0}, 1, 0.0}});
+      dead.push_back(Ni);
+      continue;
+    }
+    // anchor (host rule, identical to the kernel's) and the triangulated position
+    f->anchor_cam_id = cand.b.feats[j].anchor_cam;
+    f->anchor_clone_timestamp = f->find((size_t)f->anchor_cam_id)->m.back().t;
+    for (int k = 0; k < 3; k++) f->p_FinA[k] = touts[j].p_FinA[k], f->p_FinG[k] = touts[j].p_FinG[k];
+    const double *base = d_.region_host(cand.region + j);
+    neg_check(base, Ni);
+    const bool accepted = base[Ni + 8] > 0.5;
+    last_upd_.push_back(FeatDebug{f->featid, {f->p_FinG[0], f->p_FinG[1], f->p_FinG[2]}, accepted ? 0 : 3,
+                                  nup > 0 ? base[Ni + 3] : 0.0});
+    frame_feats_.push_back({2, last_upd_.back()});
+    if (!accepted) {
+      dead.push_back(Ni);
+      continue;
+    }
+    VarP lm = std::make_shared<Var>(V_LANDMARK, 3, 3);
+    lm->featid = f->featid;
+    lm->rep = rep_slam;
+    lm->unique_cam = f->anchor_cam_id;
+    lm->anchor_cam = f->anchor_cam_id;
+    lm->anchor_time = f->anchor_clone_timestamp;
+    const bool relr = (rep_slam == 2 || rep_slam == 4);
+    lm->set_xyz(relr ? f->p_FinA : f->p_FinG, false);
+    lm->set_xyz(relr ? f->p_FinA : f->p_FinG, true);
+    lm->id = Ni;
+    vars_.push_back(lm);
+    double HLinv[9], dl[3];
+    inv3_cofactor(outs[j].HfR, HLinv);  // the device's formula: identical H_Linv
+    const double *resinit = base + Ni + 5;
+    for (int a = 0; a < 3; a++)
+      dl[a] = HLinv[3 * a] * resinit[0] + HLinv[3 * a + 1] * resinit[1] + HLinv[3 * a + 2] * resinit[2];
+    lm->update(dl);
+    if (nup > 0) apply_dx(base);
+    slam_.insert({f->featid, lm});
+  }
+  marginalize_slots(dead);  // the rejected candidates' zeroed slots
 }
 
 }  // namespace uvhp

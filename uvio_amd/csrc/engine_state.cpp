@@ -227,13 +227,12 @@ Engine::~Engine() {
   if (rt_.h_obs) hipHostFree(rt_.h_obs);
   if (rt_.h_slam) hipHostFree(rt_.h_slam);
   if (rt_.copied) hipEventDestroy(rt_.copied);
-  void *ptrs[] = {d_.P, d_.P2, d_.T, d_.Phi, d_.Q, d_.dnc, d_.iold, d_.feats, d_.meas, d_.vars, d_.clones, d_.cams,
-                  d_.chi2, d_.H, d_.Tall, d_.partials, d_.R, d_.hidx, d_.ekf.M, d_.ekf.W, d_.ekf.S, d_.ekf.y,
+  void *ptrs[] = {d_.P, d_.P2, d_.T, d_.Phi, d_.Q, d_.dnc, d_.iold,
+                  d_.chi2, d_.H, d_.Tall, d_.partials, d_.R, d_.ekf.M, d_.ekf.W, d_.ekf.S, d_.ekf.y,
                   d_.ekf.Dinv, d_.stg_d, d_.acc, d_.shard, d_.hidx_pre, d_.chain, d_.frame, d_.chi2S, d_.uwb_reg,
                   d_.uwb_h};
   for (void *p : ptrs)
     if (p) hipFree(p);
-  if (d_.pin) hipHostFree(d_.pin);
   if (d_.shard_host) hipHostFree(d_.shard_host);
   if (d_.stg_h) hipHostFree(d_.stg_h);
   if (d_.hidx_pre_h) hipHostFree(d_.hidx_pre_h);
@@ -246,8 +245,6 @@ Engine::~Engine() {
   if (d_.aux) hipStreamDestroy(d_.aux);
   if (d_.ev_copy) hipEventDestroy(d_.ev_copy);
   if (d_.copy) hipStreamDestroy(d_.copy);
-  if (d_.ev0) hipEventDestroy(d_.ev0);
-  if (d_.ev1) hipEventDestroy(d_.ev1);
   if (d_.stream) hipStreamDestroy(d_.stream);
 }
 
@@ -265,8 +262,6 @@ void Engine::alloc_device() {
     throw HpError(UVIO_HP_E_DEVICE, "no HIP device " + std::to_string(device_));
   HP_HIP(hipSetDevice(device_));
   HP_HIP(hipStreamCreateWithFlags(&d_.stream, hipStreamNonBlocking));
-  HP_HIP(hipEventCreate(&d_.ev0));
-  HP_HIP(hipEventCreate(&d_.ev1));
   HP_HIP(hipStreamCreateWithFlags(&d_.aux, hipStreamNonBlocking));
   HP_HIP(hipEventCreateWithFlags(&d_.ev_aux_in, hipEventDisableTiming));
   HP_HIP(hipEventCreateWithFlags(&d_.ev_aux_out, hipEventDisableTiming));
@@ -299,18 +294,12 @@ void Engine::alloc_device() {
   d_.max_rows = maxf * 2 * meas_per_feat;
   d_.max_ncol = cap + 1;
   d_.ldh = (d_.max_ncol + 7) / 8 * 8;
-  dalloc(&d_.feats, maxf);
-  dalloc(&d_.meas, d_.max_meas_total);
-  dalloc(&d_.vars, d_.max_vars_total);
-  dalloc(&d_.clones, C + 4);
-  dalloc(&d_.cams, UVIO_HP_MAX_CAMS);
   dalloc(&d_.chi2, 1000);
   dalloc(&d_.H, (size_t)d_.max_rows * d_.ldh);
   dalloc(&d_.Tall, (size_t)d_.max_rows * d_.ldh);
   int maxch = std::max((d_.max_rows + 511) / 512 + 1, gram_num_chunks(2048) + 1);  // 512- or 64-row chunks
   dalloc(&d_.partials, (size_t)maxch * d_.max_ncol * d_.max_ncol);
   dalloc(&d_.R, (size_t)2 * d_.max_ncol * d_.ldh);
-  dalloc(&d_.hidx, d_.max_ncol + d_.max_rows);
   dalloc(&d_.hidx_pre, (size_t)DeviceBufs::kPreSlots * d_.max_ncol);
   HP_HIP(hipHostMalloc((void **)&d_.hidx_pre_h, sizeof(int) * DeviceBufs::kPreSlots * std::max(d_.max_ncol, 1),
                        hipHostMallocDefault));
@@ -323,9 +312,13 @@ void Engine::alloc_device() {
   dalloc(&d_.ekf.M3, (size_t)cap * 3);
   dalloc(&d_.ekf.Dinv, (size_t)(rmax / 16 + 1) * 256);
   d_.dx_bytes = sizeof(double) * (cap + 16);
-  // one frame chain holds the MSCKF batch, the SLAM chunks and the delayed initialization's two passes
-  d_.fout_cap = maxf + 3 * std::max(o_.max_slam_features, 0) + 64;
-  d_.chain_k = std::max(o_.max_slam_features, 1) + std::max(o_.max_slam_features, 1) / std::max(o_.max_slam_in_update, 1) + 4;
+  // One chain holds the MSCKF batch (at most maxf features, one region), the SLAM chunks (a result slot per
+  // landmark, at most a region each) and the delayed initialization's two passes (two slots and one region per
+  // candidate).  Landmarks and candidates each own 3 columns of P, so there are at most cap / 3 of them together:
+  // the chain's covariance check (N0 + 3 K > ldp) always binds before its region or result-slot checks.
+  const int max3 = cap / 3;
+  d_.fout_cap = maxf + 2 * max3 + 64;
+  d_.chain_k = max3 + 4;
   d_.chain_stride = (size_t)cap + 16;
   // [chain regions (reversed) | dx block (neg, dx) | fout] on the device and mirrored in pinned memory
   const size_t reg_bytes = sizeof(double) * d_.chain_k * d_.chain_stride;
@@ -338,25 +331,26 @@ void Engine::alloc_device() {
   dalloc(&d_.shard, (size_t)d_.max_ncol * d_.max_ncol + 2);
   d_.ekf.neg = (int *)d_.dxneg;
   d_.ekf.dx = d_.dxneg + 1;
-  HP_HIP(hipHostMalloc((void **)&d_.chain_host, res_bytes + sizeof(double) * 16 + 64, hipHostMallocDefault));
+  HP_HIP(hipHostMalloc((void **)&d_.chain_host, res_bytes + 64, hipHostMallocDefault));
   // chi2 table: boost::math::quantile(chi_squared(dof), 0.95) for dof 1..999 (UpdaterMSCKF.cpp:52-55)
   for (int i = 1; i < 1000; i++) chi2_table_[i] = chi2_quantile95(i);
   HP_HIP(hipMemcpy(d_.chi2, chi2_table_.data(), 1000 * sizeof(double), hipMemcpyHostToDevice));
-  // pinned staging: batch upload + small downloads
-  d_.pin_bytes = sizeof(DFeat) * maxf + sizeof(DMeas) * d_.max_meas_total + sizeof(DVar) * d_.max_vars_total +
-                 sizeof(DClone) * (C + 4) + sizeof(DCam) * UVIO_HP_MAX_CAMS + sizeof(int) * (d_.max_ncol + d_.max_rows) +
-                 sizeof(double) * (cap + 16) + sizeof(DFeatOut) * d_.fout_cap + sizeof(double) * 16 + 4096;
-  HP_HIP(hipHostMalloc(&d_.pin, d_.pin_bytes, hipHostMallocDefault));
   char *pb = (char *)d_.chain_host + reg_bytes;
   d_.neg_host = (int *)pb;  // same layout as dxneg
   d_.dx_host = (double *)(pb + sizeof(double));
   d_.fout_host = (DFeatOut *)(pb + d_.dx_bytes);
-  d_.aux_host = (double *)(pb + d_.dx_bytes + sizeof(DFeatOut) * d_.fout_cap);
-  d_.frame_bytes = sizeof(DClone) * (C + 4) + sizeof(DCam) * UVIO_HP_MAX_CAMS + sizeof(DPoseVal) * (C + 4 + UVIO_HP_MAX_CAMS) +
+  // the chain's state blob: a clone owns 6 columns of P, so there are at most cap / 6 of them
+  const int maxcl = cap / 6;
+  d_.frame_bytes = sizeof(DClone) * maxcl + sizeof(DCam) * UVIO_HP_MAX_CAMS + sizeof(DPoseVal) * (maxcl + UVIO_HP_MAX_CAMS) +
                    sizeof(double) * cap + 1024;
   dalloc(&d_.frame, d_.frame_bytes);
-  // upload staging (batch tables, Phi / Q, column maps)
-  d_.stg_cap = d_.pin_bytes + 2 * 64 * 64 * sizeof(double) + 64 * 1024;
+  // upload staging ring (batch tables, Phi / Q, column maps): one full update batch's tables and some slack
+  const size_t batch_bytes =
+      sizeof(DFeat) * maxf + sizeof(DMeas) * d_.max_meas_total + sizeof(DVar) * d_.max_vars_total +
+      sizeof(DClone) * (C + 4) + sizeof(DCam) * UVIO_HP_MAX_CAMS + sizeof(int) * (d_.max_ncol + d_.max_rows) +
+      sizeof(double) * (cap + 16) + sizeof(DFeatOut) * (maxf + 3 * std::max(o_.max_slam_features, 0) + 64) +
+      sizeof(double) * 16 + 4096;
+  d_.stg_cap = batch_bytes + 2 * 64 * 64 * sizeof(double) + 64 * 1024;
   // test hook: a smaller ring recycles every few batches (tests/test_gpu_configs.py staging test)
   if (const char *e = std::getenv("UVIO_HP_STAGE_BYTES")) d_.stg_cap = std::min(d_.stg_cap, (size_t)std::atoll(e));
   if (const char *e = std::getenv("UVIO_HP_NO_PREDETECT")) predetect_on_ = e[0] != '1';
@@ -442,11 +436,6 @@ void Engine::stage_flush(bool on_main) {
 }
 
 void Engine::dev_sync() {
-  if (d_.fout_pending) {  // feature results of a batch whose update did not read back (yet)
-    HP_HIP(hipMemcpyAsync(d_.fout_host, d_.fout, sizeof(DFeatOut) * d_.fout_pending, hipMemcpyDeviceToHost,
-                          d_.stream));
-    d_.fout_pending = 0;
-  }
   auto t0 = std::chrono::steady_clock::now();
   spin_sync(d_.stream);
   timing_.sync_wait += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -507,13 +496,9 @@ void Engine::chain_results_copy(int nreg, int fo) {
 }
 
 void Engine::read_dx(const char *who) {
-  // [neg | dx (N) | chi2, accepted of a delayed-init chi2 gate (EkfScratch::chi2_gate)]
   HPROF("read_dx");
-  // [count | dx], and the pending batch results behind them in the same copy
-  const size_t bytes = d_.fout_pending ? d_.dx_bytes + sizeof(DFeatOut) * d_.fout_pending
-                                       : sizeof(double) * (3 + (size_t)N_);
-  d_.fout_pending = 0;
-  HP_HIP(hipMemcpyAsync(d_.neg_host, d_.dxneg, bytes, hipMemcpyDeviceToHost, d_.stream));
+  // [count | dx (N)]
+  HP_HIP(hipMemcpyAsync(d_.neg_host, d_.dxneg, sizeof(double) * (3 + (size_t)N_), hipMemcpyDeviceToHost, d_.stream));
   dev_sync();
   if (*d_.neg_host > 0) throw HpError(UVIO_HP_E_NUMERIC, std::string(who) + ": negative covariance diagonal");
 }
@@ -652,65 +637,25 @@ void Engine::apply_dx(const double *dx) {
 
 // EKF update of P on the device with rows H (r x n, ld) / residual; dx applied to the host mean
 void Engine::ekf_update_rows(const double *Hdev, int ldh, int r, int n, const std::vector<int> &hidx,
-                             const double *resdev, int res_stride, double sigma2, const int *hidx_dev,
-                             const std::function<bool()> &apply, const int *gate, const double *Tdev) {
-  if (r <= 0) {
-    if (apply) apply();
-    return;
-  }
+                             const double *resdev, int res_stride, double sigma2) {
+  if (r <= 0) return;
   if (r > kMaxEkfRows) throw HpError(UVIO_HP_E_CAPACITY, "direct EKF update with more than 255 rows");
-  if (!hidx_dev) {
-    hidx_dev = stage(hidx.data(), (size_t)n);
-    stage_flush();
-  }
-  d_.ekf.gate = gate;
+  const int *hidx_dev = stage(hidx.data(), (size_t)n);
+  stage_flush();
   {
     HPROF("ekf_rows.launch");
     KScope ks(&kprof_, KC_EKF);
-    d_.ekf.Tall = Tdev;
-    d_.ekf.ldt = ldh;
     launch_ekf_update(d_.stream, d_.P, d_.ldp, N_, Hdev, ldh, r, n, hidx_dev, resdev, res_stride, sigma2, d_.ekf);
-    d_.ekf.Tall = nullptr;
     ++p_epoch_;
   }
   kprof_.credit(KC_EKF, ekf_flops(N_, n, r), ekf_bytes(N_, n, r));
   read_dx("EKFUpdate");
-  if (!apply || apply()) apply_dx(d_.dx_host);
-}
-
-// EKF update from the Gram partials of a stacked batch (compressed path, m > n)
-void Engine::ekf_update_info(int nch, int n, const std::vector<int> &hidx, double sigma2,
-                             const std::function<bool()> &apply, const int *gate, const double *partials) {
-  // the prefactor of these columns is in flight and P is unchanged since it was enqueued
-  const bool inflight = d_.pre_N >= 0;
-  const bool pre = inflight && d_.pre_N == N_ && d_.pre_hidx == hidx && d_.pre_epoch == p_epoch_;
-  d_.pre_hidx.clear();
-  d_.pre_N = -1;
-  d_.ekf.gate = gate;
-  const double *G = partials ? partials : d_.partials;
-  if (pre) {
-    HP_HIP(hipStreamWaitEvent(d_.stream, d_.ev_aux_out, 0));
-    KScope ks(&kprof_, KC_EKF);
-    launch_ekf_info_post(d_.stream, d_.P, d_.ldp, N_, G, nch, n, sigma2, d_.R, d_.ekf);
-  } else {
-    // a stale prefactor still writes the factor scratch on the side stream: order the full update after it
-    if (inflight) HP_HIP(hipStreamWaitEvent(d_.stream, d_.ev_aux_out, 0));
-    const int *dh = stage(hidx.data(), (size_t)n);
-    stage_flush();
-    KScope ks(&kprof_, KC_EKF);
-    launch_ekf_info(d_.stream, d_.P, d_.ldp, N_, G, nch, n, dh, sigma2, d_.R, d_.ekf);
-  }
-  ++p_epoch_;
-  // the timed launches: without the side-stream prefactor (Cholesky of P_II, n^3 / 3, and V, N n^2) when it ran
-  const double fl = ekf_flops(N_, n, n) - (pre ? (double)n * n * n / 3.0 + (double)N_ * n * n : 0.0);
-  kprof_.credit(KC_EKF, fl, ekf_bytes(N_, n, n));
-  read_dx("EKFUpdate");
-  if (!apply || apply()) apply_dx(d_.dx_host);
+  apply_dx(d_.dx_host);
 }
 
 // The information-form update's prefactor (launch_ekf_info_pre: P_II = L L^T, V = P[:,I] L^-T) for the
 // columns hidx of the state as it is now, on the side stream, behind everything enqueued so far; the
-// next ekf_update_info on the same columns and state size waits for it instead of factoring again.  Between
+// next information-form update (engine_chain.cpp) on the same columns and state size waits for it instead of factoring again.  Between
 // the two calls only kernels that read P may be enqueued (the feature group, chi2 gate and Gram do).
 void Engine::info_prefactor(const std::vector<int> &hidx) {
   const int n = (int)hidx.size();

@@ -613,7 +613,6 @@ int Engine::do_feature_propagate_update(double t, const std::vector<int> &camids
   }
   timing_.n_slam_delayed = (int)slam_delayed.size();
   int rc = 0;
-  auto rT4 = clk::now(), rT5 = rT4, rT6 = rT4;
   // FeatureDatabase::cleanup_measurements(margtimestep) of every feature the updaters do not read runs while
   // the device executes the chain: one feature's trimming is independent of the others', nothing between
   // the updates and the cleanup reads the trimmed (older than the marginalized clone) measurements of an
@@ -632,44 +631,25 @@ int Engine::do_feature_propagate_update(double t, const std::vector<int> &camids
       for (auto &f : h) f->held = false;
     }
   } held_guard{*this, held};
-  // the chain also carries the feature-sharded MSCKF update: over RCCL its all-reduce is enqueued; the host
-  // all-reduce (a callback, for ranks that share a GPU) waits for this rank's Gram in the middle of the enqueueing
-  if (!no_chain_) {
-    if (do_clean) {
-      held = pending_delete_;
-      for (auto &f : held) f->held = true;
-      chain_overlap_ = [this, mt_clean, &cleaned_early]() {
-        cleanup_measurements(mt_clean, true);
-        cleaned_early = true;
-      };
-    }
-    // the three updaters as one device chain with one host wait (engine_chain.cpp)
-    rc = update_frame(up, slam_upd, slam_delayed);
-    chain_overlap_ = nullptr;
-    if (rc) return rc;
-    rT6 = clk::now();
-    timing_.msckf_update = chain_times_[0];
-    timing_.slam_update = chain_times_[1];
-    timing_.slam_delayed = chain_times_[2];
-  } else {
-    rc = msckf_update(up);
-    if (rc) return rc;
-    rT4 = clk::now();
-    while (!slam_upd.empty()) {
-      size_t k = std::min((size_t)std::max(o_.max_slam_in_update, 1), slam_upd.size());
-      std::vector<FeatP> tmp(slam_upd.begin(), slam_upd.begin() + k);
-      slam_upd.erase(slam_upd.begin(), slam_upd.begin() + k);
-      rc = slam_update(tmp);
-      if (rc) return rc;
-    }
-    rT5 = clk::now();
-    rc = slam_delayed_init(slam_delayed);
-    if (rc) return rc;
-    rT6 = clk::now();
-    timing_.msckf_update = secs(rT3, rT4);
-    timing_.slam_update = secs(rT4, rT5);
-    timing_.slam_delayed = secs(rT5, rT6);
+  if (do_clean) {
+    held = pending_delete_;
+    for (auto &f : held) f->held = true;
+    chain_overlap_ = [this, mt_clean, &cleaned_early]() {
+      cleanup_measurements(mt_clean, true);
+      cleaned_early = true;
+    };
   }
+  // the three updaters as one device chain with one host wait (engine_chain.cpp); the SLAM list goes in chunks
+  // of max_slam_in_update (VioManager.cpp:533-545).  The chain also carries the feature-sharded MSCKF update:
+  // over RCCL its all-reduce is enqueued; the host all-reduce (a callback, for ranks that share a GPU) waits for
+  // this rank's Gram in the middle of the enqueueing
+  rc = update_frame(up, slam_upd, slam_delayed, (size_t)std::max(o_.max_slam_in_update, 1));
+  chain_overlap_ = nullptr;
+  if (rc) return rc;
+  const auto rT6 = clk::now();
+  timing_.msckf_update = chain_times_[0];
+  timing_.slam_update = chain_times_[1];
+  timing_.slam_delayed = chain_times_[2];
   HPROF("marg.total");
   {
     HPROF("marg.retri");
@@ -1011,126 +991,16 @@ DBatchParams Engine::batch_params(const Batch &b, double sigma_pix_sq, double ch
   return bp;
 }
 
-// Upload a batch, run the per-feature kernel and (optionally) compression; results in outs.
-// Returns the number of stacked rows written to H_all.
-int Engine::run_batch(Batch &b, int mode, double sigma_pix_sq, double chi2_mult, bool wait, std::vector<DFeatOut> &outs,
-                      bool chi2) {
-  int nf = (int)b.feats.size();
-  if (nf == 0) return 0;
-  b.chi2 = chi2;
-  if (nf > d_.max_feat || (int)b.n_meas() > d_.max_meas_total || (int)b.n_vars() > d_.max_vars_total ||
-      b.rows > d_.max_rows || b.n_canon + 1 > d_.max_ncol)
-    throw HpError(UVIO_HP_E_CAPACITY, "update batch exceeds device capacity");
-  int max_meas = 0, max_nf = 0;
-  for (auto &F : b.feats) {
-    max_meas = std::max(max_meas, F.nmeas);
-    max_nf = std::max(max_nf, F.nf);
-  }
-  if (max_meas > kMaxMeasPerFeat) throw HpError(UVIO_HP_E_CAPACITY, "too many measurements per feature");
-  size_t lds = feature_lds_bytes(max_meas, max_nf);
-  if (lds + 4096 > 160 * 1024) throw HpError(UVIO_HP_E_CAPACITY, "feature LDS footprint too large");
-  // the batch tables go up packed in one copy
-  const DFeat *t_feats = stage(b.feats.data(), b.feats.size());
-  const DMeas *t_meas = b.meas_dev ? b.meas_dev : stage(b.meas.data(), b.meas.size());
-  const DVar *t_vars = b.vars_dev ? b.vars_dev : stage(b.vars.data(), b.vars.size());
-  const DClone *t_clones = stage(b.clones.data(), b.clones.size());
-  const DCam *t_cams = stage(b.cams.data(), b.cams.size());
-  const int *t_hidx = stage(b.hidx.data(), b.hidx.size());
-  stage_flush();
-  // the measurement / variable reservation must still be intact: after a ring restart in between, the
-  // tables staged since then start at offset 0 and must end before the reservation (a ring smaller than
-  // one launch group, UVIO_HP_STAGE_BYTES, would let them overwrite it on the device)
-  if (b.meas_dev && b.stg_epoch != d_.stg_epoch && d_.stg_used > (size_t)((const char *)b.meas_dev - d_.stg_d))
-    throw HpError(UVIO_HP_E_CAPACITY, "upload staging ring restarted inside one launch group (UVIO_HP_STAGE_BYTES too small)");
-  b.hidx_dev = t_hidx;
-  DBatchParams bp = batch_params(b, sigma_pix_sq, chi2_mult);
-  const char *mdump = (mode == 0) ? std::getenv("UVIO_HP_MEAS_DUMP") : nullptr;  // debug only
-  if (mdump) HP_HIP(hipMalloc(&bp.dbg, sizeof(double) * 8 * b.n_meas()));
-  const char *tsdump = std::getenv("UVIO_HP_FEAT_TS");  // debug only: per-feature phase cycle counts
-  if (tsdump) {  // 8 k_feature phases + 4 k_chi2 phases per feature
-    HP_HIP(hipMalloc(&bp.dbg_ts, sizeof(long long) * 16 * nf));
-    HP_HIP(hipMemset(bp.dbg_ts, 0, sizeof(long long) * 16 * nf));
-  }
-  // the feature group's event pair only while kernel timing is on: a timing event between the upload and
-  // k_feature costs a dispatch gap on every batch
-  b.evtimed = o_.record_timing && kprof_.on;
-  if (b.evtimed) HP_HIP(hipEventRecord(d_.ev0, d_.stream));
-  {
-    KScope ks(&kprof_, KC_FEATURE);
-    launch_feature_linearize(d_.stream, bp, t_feats, t_meas, t_vars, t_clones, t_cams, d_.P, d_.chi2, d_.H, d_.fout,
-                             max_meas, max_nf);
-  }
-  if (chi2) {
-    int max_rows_f = 0;
-    for (auto &F : b.feats) {
-      int rows_out = (mode == 0) ? 2 * F.nmeas - 3 : 2 * F.nmeas;
-      max_rows_f = std::max(max_rows_f, rows_out - (mode >= 2 ? 3 : 0));
-    }
-    KScope ks(&kprof_, KC_CHI2);
-    // d_.R (the information-form Gram buffer, 2 max_ncol ldh doubles) holds the gathered P_can until the
-    // T GEMM has read it; the Gram reduce writes it only later on the same stream
-    launch_chi2_batch(d_.stream, bp, t_feats, d_.P, t_hidx, d_.H, b.rows, d_.Tall, d_.chi2, d_.fout,
-                      max_rows_f, d_.acc, d_.R, &d_.chi2S, &d_.chi2S_cap);
-  }
-  if (b.evtimed) HP_HIP(hipEventRecord(d_.ev1, d_.stream));
-  d_.fout_pending = nf;  // copied with the next readback (read_dx) or before the next wait (dev_sync)
-  if (!wait && !tsdump && !mdump) return b.rows;  // the caller's next sync completes the batch (finish_batch)
-  dev_sync();
-  finish_batch(b, mode, outs);
-  if (tsdump) {
-    std::vector<long long> h(16 * (size_t)nf);
-    HP_HIP(hipMemcpy(h.data(), bp.dbg_ts, sizeof(long long) * h.size(), hipMemcpyDeviceToHost));
-    HP_HIP(hipFree(bp.dbg_ts));
-    FILE *fp = std::fopen(tsdump, "ab");
-    for (int i = 0; i < nf; i++) {
-      long long rec[16] = {mode, nf, b.feats[i].nmeas, b.feats[i].nf};
-      for (int k = 0; k < 12; k++) rec[4 + k] = h[16 * (size_t)i + k];
-      std::fwrite(rec, sizeof(long long), 16, fp);
-    }
-    std::fclose(fp);
-  }
-  if (mdump) {
-    std::vector<double> h(8 * b.n_meas());
-    HP_HIP(hipMemcpy(h.data(), bp.dbg, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
-    HP_HIP(hipFree(bp.dbg));
-    FILE *fp = std::fopen(mdump, "ab");
-    for (int i = 0; i < nf; i++) {
-      if (outs[i].status != 0) continue;
-      for (int k = 0; k < b.feats[i].nmeas; k++) {
-        double fid = (double)i;
-        std::fwrite(&fid, sizeof(double), 1, fp);
-        std::fwrite(h.data() + 8 * (size_t)(b.feats[i].meas_off + k), sizeof(double), 8, fp);
-      }
-    }
-    std::fclose(fp);
-  }
-  return b.rows;
-}
-
-// per-feature results of a batch whose readback has completed (after a device sync), plus the feature
-// group's event timing
+// per-feature results of a batch whose readback has completed (after a device sync), and the kernel classes'
+// FLOP / byte credit
 void Engine::finish_batch(Batch &b, int mode, std::vector<DFeatOut> &outs) {
   const int nf = (int)b.feats.size();
   outs.assign(d_.fout_host + b.fout_off, d_.fout_host + b.fout_off + nf);
   if (b.finished) return;
   b.finished = true;
-  if (b.evtimed) {
-    float ms = 0.f;
-    HP_HIP(hipEventElapsedTime(&ms, d_.ev0, d_.ev1));
-    timing_.k_feat_launches += 1;
-    timing_.k_feat_s += 1e-3 * ms;
-    // algorithmic FP64 FLOPs (SURVEY.md §8(d) F_feat) of the features that reached the projection
-    for (int i = 0; i < nf && mode != 2; i++) {  // mode 2 triangulates only
-      if (outs[i].status == 1 || outs[i].status == 2) continue;
-      double rows = 2.0 * b.feats[i].nmeas, nfc = b.feats[i].nf;
-      double r = (mode == 1) ? rows : rows - 3.0;
-      double refl = (mode == 1) ? 0.0 : 12.0 * rows * (nfc + 4.0);
-      const double chi2 = b.chi2 ? 2.0 * r * nfc * nfc + 2.0 * r * r * nfc + r * r * r / 3.0 : 0.0;
-      timing_.k_feat_flops += refl + chi2;
-    }
-  }
   if (kprof_.on) {
-    // the same F_feat split by class: reflections -> k_feature, the chi2 terms -> the chi2 group; bytes =
+    // algorithmic FP64 FLOPs (SURVEY.md §8(d) F_feat: 3 Householder reflections 12 (2 m_f)(n_f + 4), chi2
+    // 2 r n^2 + 2 r^2 n + r^3 / 3 per feature) split by class: reflections -> k_feature, the chi2 terms -> the chi2 group; bytes =
     // the rows each writes (k_feature) / reads with their T rows (chi2) plus the P block gathered
     double fl = 0, fb = 0, cl = 0, cb = 0;
     for (int i = 0; i < nf; i++) {
@@ -1156,382 +1026,6 @@ void Engine::gram(int m, int ncol, int *nch) {
     launch_gram(d_.stream, d_.H, m, ncol, d_.ldh, d_.partials, nch);
   }
   kprof_.credit(KC_GRAM, (double)m * ncol * (ncol + 1), 8.0 * ((double)m * ncol + (double)*nch * ncol * ncol));
-}
-
-// UpdaterMSCKF::update (UpdaterMSCKF.cpp:58-295)
-int Engine::msckf_update(std::vector<FeatP> &fv) {
-  stage_ = "UpdaterMSCKF::update";
-  last_msckf_.clear();
-  if (fv.empty()) return 0;
-  HPROF("msckf.total");
-  std::vector<double> clonetimes;
-  for (auto &c : clones_) clonetimes.push_back(c.first);
-  std::vector<uint8_t> few(fv.size());
-  pool_.parallel_for(fv.size(), 64, [&](size_t b0, size_t e0) {
-    for (size_t i = b0; i < e0; i++) {
-      fv[i]->clean_old_measurements(clonetimes);
-      few[i] = fv[i]->count() < 2;
-    }
-  });
-  std::vector<FeatP> keep;
-  for (size_t i = 0; i < fv.size(); i++) {
-    if (few[i])
-      fv[i]->to_delete = true;
-    else
-      keep.push_back(fv[i]);
-  }
-  fv = keep;
-  if (fv.empty()) return 0;
-  if (o_.feat_rep_msckf != 0 && o_.feat_rep_msckf != 4)
-    throw HpError(UVIO_HP_E_CONFIG, "feat_rep_msckf: only GLOBAL_3D / ANCHORED_MSCKF_INVERSE_DEPTH are implemented");
-  if (shard_.enabled && (int)fv.size() >= shard_.min_features) return msckf_update_sharded(fv);
-  Batch b;
-  {
-    HPROF("msckf.build");
-    build_clone_cam_tables(b, false);
-    add_features_to_batch(b, fv, 0, fv.size(), 0, o_.feat_rep_msckf);
-  }
-  // compressed (information-form) update ahead: its P_II factor and V start now, beside the feature group
-  PrefactorJoin pj(this);
-  if (b.rows > b.n_canon || b.rows > kMaxEkfRows) info_prefactor(b.hidx);
-  // The update is enqueued right behind the feature group: rejected features already have zero rows in
-  // H_all and the device skips the P update when no feature was accepted (d_.acc), so the host reads the
-  // per-feature results with the update's dx instead of waiting for them in between.
-  std::vector<DFeatOut> outs;
-  const double s2 = o_.msckf_sigma_pix * o_.msckf_sigma_pix;
-  int m;
-  {
-    HPROF("msckf.run_batch");
-    m = run_batch(b, 0, s2, o_.msckf_chi2_multipler, false, outs);
-  }
-  const int n = b.n_canon, ncol = n + 1;
-  auto results = [&]() {
-    HPROF("msckf.results");
-    finish_batch(b, 0, outs);
-    int acc = 0, acc_rows = 0;
-    for (size_t i = 0; i < outs.size(); i++) {
-      last_msckf_.push_back(FeatDebug{fv[i]->featid, {outs[i].p_FinG[0], outs[i].p_FinG[1], outs[i].p_FinG[2]},
-                                      outs[i].status == 2 ? 1 : outs[i].status, outs[i].chi2});
-      frame_feats_.push_back({0, last_msckf_.back()});
-      fv[i]->to_delete = true;
-      for (int k = 0; k < 3; k++) fv[i]->p_FinG[k] = outs[i].p_FinG[k], fv[i]->p_FinA[k] = outs[i].p_FinA[k];
-      if (outs[i].status == 0) acc++, acc_rows += outs[i].rows;
-    }
-    timing_.msckf_rows = acc_rows;
-    timing_.msckf_cols = b.n_canon;
-    if (const char *dump = std::getenv("UVIO_HP_DUMP")) {  // debug: projected rows per feature
-      int nc = b.n_canon + 1;
-      std::vector<double> Hh((size_t)std::max(m, 1) * nc);
-      if (m > 0)
-        HP_HIP(hipMemcpy2D(Hh.data(), sizeof(double) * nc, d_.H, sizeof(double) * d_.ldh, sizeof(double) * nc, m,
-                           hipMemcpyDeviceToHost));
-      FILE *fp = std::fopen(dump, "ab");
-      for (size_t i = 0; i < outs.size(); i++) {
-        if (outs[i].status != 0) continue;
-        std::vector<double> hdr = {(double)fv[i]->featid, (double)outs[i].rows, (double)b.n_canon};
-        for (int j = 0; j < b.n_canon; j++) hdr.push_back(b.hidx[j]);
-        std::fwrite(hdr.data(), sizeof(double), hdr.size(), fp);
-        std::fwrite(Hh.data() + (size_t)b.feats[i].row_off * nc, sizeof(double), (size_t)outs[i].rows * nc, fp);
-      }
-      std::fclose(fp);
-    }
-    return acc > 0;
-  };
-  if (m < 1) {
-    dev_sync();
-    results();
-    return 0;
-  }
-  if (m > n || m > kMaxEkfRows) {
-    // measurement compression (UpdaterHelper.cpp:456-487) + EKFUpdate on the compressed system, carried
-    // out in information form on G = [H r]^T [H r] (see launch_ekf_info)
-    int nch = 0;
-    gram(m, ncol, &nch);
-    ekf_update_info(nch, n, b.hidx, s2, results, d_.acc);
-  } else {
-    ekf_update_rows(d_.H, d_.ldh, m, n, b.hidx, d_.H + n, d_.ldh, s2, b.hidx_dev, results, d_.acc, d_.Tall);
-  }
-  return 0;
-}
-
-// UpdaterSLAM::update (UpdaterSLAM.cpp:253-479)
-int Engine::slam_update(std::vector<FeatP> &fv) {
-  stage_ = "UpdaterSLAM::update";
-  if (fv.empty()) return 0;
-  std::vector<double> clonetimes;
-  for (auto &c : clones_) clonetimes.push_back(c.first);
-  std::vector<FeatP> keep;
-  for (auto &f : fv) {
-    f->clean_old_measurements(clonetimes);
-    int ct = f->count();
-    if (ct < 1)
-      f->to_delete = true;
-    else
-      keep.push_back(f);
-  }
-  fv = keep;
-  if (fv.empty()) return 0;
-  Batch b;
-  build_clone_cam_tables(b, true);
-  // landmark columns appended to the canonical set
-  std::vector<int> lm_canon;
-  for (auto &f : fv) {
-    const VarP &lm = slam_.at(f->featid);
-    lm_canon.push_back(b.n_canon);
-    for (int k = 0; k < lm->size; k++) b.hidx.push_back(lm->id + k);
-    b.n_canon += lm->size;
-  }
-  for (size_t i = 0; i < fv.size(); i++) {
-    const VarP &lm = slam_.at(fv[i]->featid);
-    if (lm->rep != 0 && lm->rep != 2 && lm->rep != 4)
-      throw HpError(UVIO_HP_E_CONFIG, "feat_rep_slam: representation not implemented");
-    add_feature(this, fv[i], 1, lm->rep, o_, b.cams, b.slot_of_time, b.clones, b.feats, b.meas, b.vars, b.rows,
-                lm.get(), lm_canon[i]);
-  }
-  // enqueued behind the feature group as in msckf_update (rejected rows are zero, d_.acc gates P)
-  PrefactorJoin pj(this);
-  if (b.rows > b.n_canon || b.rows > kMaxEkfRows) info_prefactor(b.hidx);
-  std::vector<DFeatOut> outs;
-  const double s2 = o_.slam_sigma_pix * o_.slam_sigma_pix;
-  const int m = run_batch(b, 1, s2, o_.slam_chi2_multipler, false, outs);
-  const int n = b.n_canon, ncol = n + 1;
-  last_upd_.clear();
-  auto results = [&]() {
-    finish_batch(b, 1, outs);
-    int acc = 0;
-    for (size_t i = 0; i < outs.size(); i++) {
-      last_upd_.push_back(FeatDebug{fv[i]->featid, {0.0, 0.0, 0.0}, outs[i].status == 2 ? 1 : outs[i].status, outs[i].chi2});
-      frame_feats_.push_back({1, last_upd_.back()});
-      fv[i]->to_delete = true;
-      if (outs[i].status == 3) slam_.at(fv[i]->featid)->fail_count++;
-      if (outs[i].status == 0) acc++;
-    }
-    return acc > 0;
-  };
-  if (m < 1) {
-    dev_sync();
-    results();
-    return 0;
-  }
-  if (m > n || m > kMaxEkfRows) {
-    int nch = 0;
-    gram(m, ncol, &nch);
-    ekf_update_info(nch, n, b.hidx, s2, results, d_.acc);
-  } else {
-    ekf_update_rows(d_.H, d_.ldh, m, n, b.hidx, d_.H + n, d_.ldh, s2, b.hidx_dev, results, d_.acc, d_.Tall);
-  }
-  return 0;
-}
-
-// UpdaterSLAM::delayed_init (UpdaterSLAM.cpp:61-251) + StateHelper::initialize (StateHelper.cpp:393-482).
-// Triangulation of the whole batch runs first (as in the reference); each accepted landmark then
-// initializes and updates the state before the next one is linearized.
-int Engine::slam_delayed_init(std::vector<FeatP> &fv) {
-  stage_ = "UpdaterSLAM::delayed_init";
-  if (fv.empty()) return 0;
-  std::vector<double> clonetimes;
-  for (auto &c : clones_) clonetimes.push_back(c.first);
-  std::vector<FeatP> keep;
-  for (auto &f : fv) {
-    f->clean_old_measurements(clonetimes);
-    if (f->count() < 2)
-      f->to_delete = true;
-    else
-      keep.push_back(f);
-  }
-  fv = keep;
-  if (fv.empty()) return 0;
-  int rep = o_.feat_rep_slam;
-  if (rep != 0 && rep != 2 && rep != 4) throw HpError(UVIO_HP_E_CONFIG, "feat_rep_slam: representation not implemented");
-  double s2 = o_.slam_sigma_pix * o_.slam_sigma_pix;
-  last_upd_.clear();
-  // 1) triangulate + refine all features against the pre-update state (UpdaterSLAM.cpp:119-141)
-  HPROF("di.total");
-  std::vector<DFeatOut> tri;
-  {
-    HPROF("di.tri");
-    Batch b;
-    build_clone_cam_tables(b, false);
-    for (auto &f : fv)
-      add_feature(this, f, 2, rep, o_, b.cams, b.slot_of_time, b.clones, b.feats, b.meas, b.vars, b.rows, nullptr, -1);
-    // triangulation only: the rows and chi2 come from the per-feature mode-3 linearization below
-    run_batch(b, 2, s2, o_.slam_chi2_multipler, true, tri, false);
-  }
-  std::vector<size_t> cand;
-  for (size_t i = 0; i < fv.size(); i++) {
-    FeatP &f = fv[i];
-    if (tri[i].status == 1 || tri[i].status == 2) {
-      f->to_delete = true;
-      last_upd_.push_back(FeatDebug{f->featid, {0.0, 0.0, 0.0}, tri[i].status, 0.0});
-      frame_feats_.push_back({2, FeatDebug{f->featid, {0.0, 0.0, 0.0}, 1, 0.0}});
-      continue;
-    }
-    // anchor (host rule, identical to the kernel's) and triangulated position
-    size_t anchor_cam = 0, most = 0;
-    for (auto &p : f->tracks)
-      if (p.m.size() > most) anchor_cam = p.cam, most = p.m.size();
-    f->anchor_cam_id = (int)anchor_cam;
-    f->anchor_clone_timestamp = f->find(anchor_cam)->m.back().t;
-    for (int k = 0; k < 3; k++) f->p_FinA[k] = tri[i].p_FinA[k], f->p_FinG[k] = tri[i].p_FinG[k];
-    cand.push_back(i);
-  }
-  // 2) per candidate, in order: linearize at the current state, initialize_invertible, the EKF update of the
-  // remaining rows behind StateHelper::initialize's chi2 test -- as device chains of up to chain_k candidates
-  for (size_t c0 = 0; c0 < cand.size(); c0 += (size_t)d_.chain_k) {
-    std::vector<size_t> part(cand.begin() + c0, cand.begin() + std::min(cand.size(), c0 + (size_t)d_.chain_k));
-    HPROF("di.chain");
-    int rc = slam_delayed_chain(fv, part, rep, s2);
-    if (rc) return rc;
-  }
-  return 0;
-}
-
-// The delayed initializations of one frame (StateHelper::initialize per candidate, StateHelper.cpp:393-482)
-// as one device chain with one host wait.  Candidate j is linearized (mode 3: at the batch triangulation,
-// the current clone / camera values), its landmark is appended by initialize_invertible in a FIXED slot
-// N0 + 3 j, its remaining rows update the state behind the chi2 test of their own factor (the S of
-// StateHelper::initialize's test, StateHelper.cpp:451-470, is the S the update factors), and k_chain_apply
-// then either moves the device clone / camera tables by the update's dx (the next candidate linearizes at
-// the updated state, as the reference's loop does) or clears the slot of a rejected candidate: a zero slot
-// has zero rows in every later M and K, so it changes nothing until the host marginalizes it afterwards
-// (StateHelper::marginalize, the same exact copy-compaction as any other variable).  The host then replays
-// the candidates in order from one readback: landmark values (H_finit^-1 times the init residual), the
-// updates' dx on its mean, the landmark set.
-int Engine::slam_delayed_chain(std::vector<FeatP> &fv, const std::vector<size_t> &idx, int rep, double s2) {
-  const int K = (int)idx.size();
-  if (K == 0) return 0;
-  const int N0 = N_;
-  if (N0 + 3 * K > d_.ldp) throw HpError(UVIO_HP_E_CAPACITY, "covariance capacity exceeded");
-  Batch b;
-  {
-    HPROF("di.prep");
-    build_clone_cam_tables(b, false);
-    for (size_t i : idx)
-      add_feature(this, fv[i], 3, rep, o_, b.cams, b.slot_of_time, b.clones, b.feats, b.meas, b.vars, b.rows, nullptr, -1);
-  }
-  if ((int)b.feats.size() > d_.max_feat || (int)b.n_meas() > d_.max_meas_total || (int)b.n_vars() > d_.max_vars_total ||
-      b.rows > d_.max_rows || b.n_canon + 1 > d_.max_ncol)
-    throw HpError(UVIO_HP_E_CAPACITY, "delayed-initialization chain exceeds device capacity");
-  for (int j = 0; j < K; j++) {  // mode 3 linearizes at the batch triangulation (p_in = p_FinA, p_in_fej = p_FinG)
-    const FeatP &f = fv[idx[j]];
-    for (int k = 0; k < 3; k++) b.feats[j].p_in[k] = f->p_FinA[k], b.feats[j].p_in_fej[k] = f->p_FinG[k];
-    if (b.feats[j].nmeas > kMaxMeasPerFeat) throw HpError(UVIO_HP_E_CAPACITY, "too many measurements per feature");
-  }
-  // the pose values behind the clone / camera tables (k_chain_apply updates them in place)
-  std::vector<DPoseVal> cv(b.clones.size()), camv(b.cams.size());
-  {
-    size_t s = 0;
-    for (auto &c : clones_) {
-      for (int k = 0; k < 4; k++) cv[s].q[k] = c.second->val[k];
-      for (int k = 0; k < 3; k++) cv[s].p[k] = c.second->val[4 + k];
-      cv[s].pid = c.second->id;
-      s++;
-    }
-    for (size_t c = 0; c < camv.size(); c++) {
-      const VarP &pose = calib_pose_.at((int)c);
-      for (int k = 0; k < 4; k++) camv[c].q[k] = pose->val[k];
-      for (int k = 0; k < 3; k++) camv[c].p[k] = pose->val[4 + k];
-      camv[c].pid = pose->id;
-    }
-  }
-  const DFeat *t_feats = stage(b.feats.data(), b.feats.size());
-  const DMeas *t_meas = stage(b.meas.data(), b.meas.size());
-  const DVar *t_vars = stage(b.vars.data(), b.vars.size());
-  DClone *t_clones = const_cast<DClone *>(stage(b.clones.data(), b.clones.size()));
-  DCam *t_cams = const_cast<DCam *>(stage(b.cams.data(), b.cams.size()));
-  DPoseVal *t_cv = const_cast<DPoseVal *>(stage(cv.data(), cv.size()));
-  DPoseVal *t_camv = const_cast<DPoseVal *>(stage(camv.data(), camv.size()));
-  const int *t_hidx = stage(b.hidx.data(), b.hidx.size());
-  stage_flush();
-  DBatchParams bp = batch_params(b, s2, o_.slam_chi2_multipler);
-  bp.nfeat = 1;
-  bp.gate_out = d_.acc;  // the candidate's linearization status: gates initialize_invertible and its update
-  const int n = b.n_canon;
-  const size_t st = d_.chain_stride;
-  {
-    HPROF("di.enqueue");
-    for (int j = 0; j < K; j++) {
-      const DFeat &F = b.feats[j];
-      const int Ni = N0 + 3 * j, nup = 2 * F.nmeas - 3;
-      {
-        KScope ks(&kprof_, KC_FEATURE);
-        launch_feature_linearize(d_.stream, bp, t_feats + j, t_meas, t_vars, t_clones, t_cams, d_.P, d_.chi2, d_.H,
-                                 d_.fout + j, F.nmeas, F.nf);
-      }
-      EkfScratch sc = d_.ekf;
-      sc.dx = d_.region_dev(j);
-      double *Hrow = d_.H + (size_t)F.row_off * d_.ldh;
-      // initialize_invertible with rows 0..2 (H_Linv from the feature's H_finit); its residual column lands in
-      // the candidate's region behind the chi2 gate's [chi2, accepted]
-      launch_init_invertible(d_.stream, d_.P, d_.ldp, Ni, Hrow, d_.ldh, n, t_hidx, nullptr, s2, sc, d_.fout + j, d_.acc,
-                             sc.dx + Ni + 5);
-      if (nup > 0) {
-        sc.chi2_gate = d_.acc;
-        sc.chi2_thr = o_.slam_chi2_multipler * chi2_table_[std::min(2 * F.nmeas, 999)];
-        sc.gate = nullptr;
-        KScope ks(&kprof_, KC_EKF);
-        launch_ekf_update(d_.stream, d_.P, d_.ldp, Ni + 3, Hrow + 3 * (size_t)d_.ldh, d_.ldh, nup, n, t_hidx,
-                          Hrow + 3 * (size_t)d_.ldh + n, d_.ldh, s2, sc);
-      }
-      if (nup > 0) kprof_.credit(KC_EKF, ekf_flops(Ni + 3, n, nup), ekf_bytes(Ni + 3, n, nup));
-      launch_chain_apply(d_.stream, d_.fout + j, d_.acc, nup > 0 ? sc.neg : nullptr, nup > 0 ? sc.dx : nullptr,
-                         t_clones, t_cv, (int)b.clones.size(), t_cams, t_camv, (int)b.cams.size(),
-                         o_.do_calib_camera_pose, o_.do_calib_camera_intrinsics, nullptr, 0, d_.P, d_.ldp, Ni + 3, Ni,
-                         sc.dx + Ni + 8);
-    }
-    ++p_epoch_;
-    chain_results_copy(K, K);
-    d_.fout_pending = 0;
-  }
-  dev_sync();
-  // replay on the host mean, candidate by candidate
-  HPROF("di.replay");
-  N_ = N0 + 3 * K;
-  std::vector<int> dead;
-  for (int j = 0; j < K; j++) {
-    FeatP &f = fv[idx[j]];
-    const DFeat &F = b.feats[j];
-    const DFeatOut &o1 = d_.fout_host[j];
-    const int Ni = N0 + 3 * j, nup = 2 * F.nmeas - 3;
-    const double *base = d_.region_host(j);
-    if (base[Ni + 9] > 0.5) throw HpError(UVIO_HP_E_NUMERIC, "EKFUpdate: negative covariance diagonal");
-    const bool accepted = base[Ni + 8] > 0.5;
-    f->to_delete = true;
-    last_upd_.push_back(FeatDebug{f->featid, {f->p_FinG[0], f->p_FinG[1], f->p_FinG[2]}, accepted ? 0 : 3,
-                                  nup > 0 ? base[Ni + 3] : 0.0});
-    frame_feats_.push_back({2, last_upd_.back()});
-    if (!accepted) {
-      dead.push_back(Ni);
-      continue;
-    }
-    VarP lm = std::make_shared<Var>(V_LANDMARK, 3, 3);
-    lm->featid = f->featid;
-    lm->rep = rep;
-    lm->unique_cam = f->anchor_cam_id;
-    lm->anchor_cam = f->anchor_cam_id;
-    lm->anchor_time = f->anchor_clone_timestamp;
-    const bool relr = (rep == 2 || rep == 4);
-    lm->set_xyz(relr ? f->p_FinA : f->p_FinG, false);
-    lm->set_xyz(relr ? f->p_FinA : f->p_FinG, true);
-    lm->id = Ni;
-    vars_.push_back(lm);
-    double HLinv[9], dl[3];
-    inv3_cofactor(o1.HfR, HLinv);  // the device's formula: identical H_Linv
-    const double *resinit = base + Ni + 5;
-    for (int a = 0; a < 3; a++)
-      dl[a] = HLinv[3 * a] * resinit[0] + HLinv[3 * a + 1] * resinit[1] + HLinv[3 * a + 2] * resinit[2];
-    lm->update(dl);
-    if (nup > 0) apply_dx(base);
-    slam_.insert({f->featid, lm});
-  }
-  // the rejected candidates' (zeroed) slots leave the covariance, last first
-  for (size_t k = dead.size(); k-- > 0;) {
-    VarP ph = std::make_shared<Var>(V_LANDMARK, 3, 3);
-    ph->id = dead[k];
-    vars_.push_back(ph);
-    marginalize(ph);
-  }
-  return 0;
 }
 
 // UpdaterSLAM::change_anchors / perform_anchor_change (UpdaterSLAM.cpp:481-647)

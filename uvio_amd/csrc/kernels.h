@@ -228,7 +228,7 @@ struct DPoseVal {
   double q[4], p[3];
   int pid, pad;
 };
-// One step of a device update chain (Engine::update_frame, Engine::slam_delayed_chain): the update's acceptance
+// One step of a device update chain (Engine::update_frame): the update's acceptance
 // (fout's linearization status if given, the gate if given: accepted rows / the chi2 test of its factor) into
 // out[0], its negative-diagonal count into out[1]; accepted with an update (dx): the clone / camera tables
 // the next batch is linearized against get the update (Var::update + quat_2_Rot, the host's formulas) and the

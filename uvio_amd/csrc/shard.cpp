@@ -11,6 +11,9 @@
 // cfg5 (n = 242), latency-bound; the work it splits is the per-feature linearization, chi2 gate and the
 // Gram over ~80k stacked rows.
 //
+// This file holds the communicator, the partition and the all-reduce; the sharded update itself is enqueued with
+// the rest of the update chain (Engine::update_frame, engine_chain.cpp).
+//
 // RCCL is reached through dlopen: the library has no link-time dependency on it, and in a process where
 // PyTorch already loaded its bundled RCCL that copy is reused instead of a second one being mapped.
 #include <dlfcn.h>
@@ -149,52 +152,6 @@ void Engine::shard_allreduce(double *dev, size_t count) {
   if (shard_.host_fn(d_.shard_host, count, shard_.host_user) != 0)
     throw HpError(UVIO_HP_E_DEVICE, "feature-shard all-reduce callback failed");
   HP_HIP(hipMemcpyAsync(dev, d_.shard_host, sizeof(double) * count, hipMemcpyHostToDevice, d_.stream));
-}
-
-// UpdaterMSCKF::update with the features split across ranks.  fv: the features after the reference's
-// clean_old_measurements / count filter (identical on every rank); this rank linearizes its chunk.
-int Engine::msckf_update_sharded(std::vector<FeatP> &fv) {
-  const int F = (int)fv.size();
-  std::vector<int> rows(F), bounds(shard_.world + 1);
-  for (int i = 0; i < F; i++) rows[i] = 2 * fv[i]->count() - 3;
-  shard_partition(rows.data(), F, shard_.world, bounds.data());
-  const int lo = bounds[shard_.rank], hi = bounds[shard_.rank + 1];
-  Batch b;
-  build_clone_cam_tables(b, false);
-  add_features_to_batch(b, fv, (size_t)lo, (size_t)hi, 0, o_.feat_rep_msckf);
-  // the information-form update always follows: its P_II factor and V run beside this rank's feature
-  // group and the all-reduce (Engine::info_prefactor)
-  PrefactorJoin pj(this);
-  info_prefactor(b.hidx);
-  std::vector<DFeatOut> outs;
-  const double s2 = o_.msckf_sigma_pix * o_.msckf_sigma_pix;
-  const int m = run_batch(b, 0, s2, o_.msckf_chi2_multipler, false, outs);
-  const int n = b.n_canon, ncol = n + 1;
-  int nch = 0;
-  if (m > 0) gram(m, ncol, &nch);
-  const size_t count = (size_t)ncol * ncol + 2;
-  launch_shard_pack(d_.stream, d_.partials, nch, ncol, d_.fout, (int)b.feats.size(), d_.acc, d_.shard);
-  shard_allreduce(d_.shard, count);
-  launch_shard_unpack(d_.stream, d_.shard, ncol, d_.acc);
-  double *tot_host = d_.aux_host + 4;  // [accepted, rows] of all ranks, read back with dx
-  HP_HIP(hipMemcpyAsync(tot_host, d_.shard + (size_t)ncol * ncol, 2 * sizeof(double), hipMemcpyDeviceToHost,
-                        d_.stream));
-  auto results = [&]() {
-    finish_batch(b, 0, outs);
-    for (size_t i = 0; i < outs.size(); i++) {
-      const FeatP &f = fv[lo + i];
-      last_msckf_.push_back(FeatDebug{f->featid, {outs[i].p_FinG[0], outs[i].p_FinG[1], outs[i].p_FinG[2]},
-                                      outs[i].status == 2 ? 1 : outs[i].status, outs[i].chi2});
-      frame_feats_.push_back({0, last_msckf_.back()});
-      for (int k = 0; k < 3; k++) f->p_FinG[k] = outs[i].p_FinG[k], f->p_FinA[k] = outs[i].p_FinA[k];
-    }
-    for (auto &f : fv) f->to_delete = true;
-    timing_.msckf_rows = (int)(tot_host[1] + 0.5);
-    timing_.msckf_cols = n;
-    return tot_host[0] > 0.5;
-  };
-  ekf_update_info(1, n, b.hidx, s2, results, d_.acc, d_.shard);
-  return 0;
 }
 
 }  // namespace uvhp
