@@ -151,6 +151,48 @@ __device__ __forceinline__ dbl4 tile_chain(int kbeg, int kend, int kq, LA la, LB
   return acc;
 }
 
+// tile_chain over the 4-wide k-steps whose bit is set in a 128-bit mask (m0: steps 0 .. 63, m1: steps 64 .. 127; step
+// s covers k = 4 s .. 4 s + 3), in ascending order, the loads of up to U set steps issued before their MFMAs.  For a
+// mask that holds every step in which an operand can be non-zero (a structural superset) the result is tile_chain's
+// bit for bit: a skipped step would add 0 * b = +-0 at the same place of the same ascending chain, and the
+// accumulator, which starts at +0, is never -0 (x + -x = +0 in round-to-nearest), so adding +-0 leaves it as it is.
+// The mask must be uniform over the wave (kmask_uniform): the step indices are scalar.
+__device__ __forceinline__ unsigned long long kmask_uniform(unsigned long long v) {
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+  return ((unsigned long long)hi << 32) | lo;
+}
+template <int U = 16, class LA, class LB>
+__device__ __forceinline__ dbl4 tile_chain_masked(unsigned long long m0, unsigned long long m1, int kend, int kq, LA la,
+                                                  LB lb, dbl4 acc) {
+  while (m0 | m1) {
+    int ks[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      int s = -1;
+      if (m0) {
+        s = __builtin_ctzll(m0);
+        m0 &= m0 - 1;
+      } else if (m1) {
+        s = 64 + __builtin_ctzll(m1);
+        m1 &= m1 - 1;
+      }
+      ks[u] = s;
+    }
+    double a[U], b[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int k = 4 * ks[u] + kq;
+      const bool in = ks[u] >= 0 && k < kend;
+      a[u] = in ? la(k) : 0.0;
+      b[u] = in ? lb(k) : 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < U; u++)
+      if (ks[u] >= 0) acc = mfma4(a[u], b[u], acc);
+  }
+  return acc;
+}
+
 __device__ __forceinline__ int xcd_swizzle(int orig, int nwg) {
   const int q = nwg / 8, r = nwg % 8, x = orig % 8;
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + orig / 8;

@@ -715,6 +715,8 @@ class Engine {
     std::vector<DClone> clones;
     std::vector<DCam> cams;
     std::vector<int> hidx;     // canonical column -> covariance id
+    // SLAM chunks: the k-step masks of DBatchParams::kmask (two words per feature, then two per 16-row tile)
+    std::vector<unsigned long long> kmask;
     const int *hidx_dev = nullptr;  // its staged device copy
     bool finished = false;          // per-feature results read back (finish_batch)
     bool chi2 = true;               // the batch chi2 kernels ran

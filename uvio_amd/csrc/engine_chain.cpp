@@ -73,6 +73,7 @@ struct Engine::ChainItem {
   const DMeas *t_meas = nullptr;
   const DVar *t_vars = nullptr;
   const int *t_hidx = nullptr;
+  const unsigned long long *t_kmask = nullptr;
 };
 
 int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, std::vector<FeatP> &delayed,
@@ -207,6 +208,7 @@ int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, s
     it.t_vars = b.vars_dev ? b.vars_dev : stage(b.vars.data(), b.vars.size());
     it.t_hidx = stage(b.hidx.data(), b.hidx.size());
     b.hidx_dev = it.t_hidx;
+    it.t_kmask = b.kmask.empty() ? nullptr : stage(b.kmask.data(), b.kmask.size());
     it.staged = true;
   };
   // the bytes a group of batches adds to the ring: staged together (one copy) when they fit behind what it
@@ -216,7 +218,8 @@ int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, s
     size_t need = 0;
     for (ChainItem *it : g) {
       const Batch &b = it->b;
-      need += al(sizeof(DFeat) * b.feats.size()) + al(sizeof(int) * b.hidx.size());
+      need += al(sizeof(DFeat) * b.feats.size()) + al(sizeof(int) * b.hidx.size()) +
+              al(sizeof(unsigned long long) * b.kmask.size());
       if (!b.meas_dev) need += al(sizeof(DMeas) * b.meas.size());
       if (!b.vars_dev) need += al(sizeof(DVar) * b.vars.size());
     }
@@ -310,6 +313,7 @@ int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, s
     DBatchParams bp = batch_params(b, s2, mult);
     bp.xv = fr_xv;
     bp.tri_in = tri_in;
+    bp.kmask = it.t_kmask;
     const char *tsdump = std::getenv("UVIO_HP_FEAT_TS");  // debug only: per-feature phase cycle counts
     if (tsdump) {                                          // 8 k_feature + 4 k_chi2 stamps per feature
       HP_HIP(hipMalloc(&bp.dbg_ts, sizeof(long long) * 16 * nf));
@@ -318,14 +322,14 @@ int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, s
     {
       KScope ks(&kprof_, KC_FEATURE);
       launch_feature_linearize(d_.stream, bp, it.t_feats, it.t_meas, it.t_vars, fr_cl, fr_cam, d_.P, d_.chi2, d_.H,
-                               d_.fout + b.fout_off, max_meas, max_nf);
+                               d_.fout + b.fout_off, max_meas, max_nf, chi2 ? d_.acc : nullptr);
     }
     if (chi2) {
       int max_rows_f = 0;
       for (auto &F : b.feats) max_rows_f = std::max(max_rows_f, (mode == 0) ? 2 * F.nmeas - 3 : 2 * F.nmeas);
       KScope ks(&kprof_, KC_CHI2);
       launch_chi2_batch(d_.stream, bp, it.t_feats, d_.P, it.t_hidx, d_.H, b.rows, d_.Tall, d_.chi2, d_.fout + b.fout_off,
-                        max_rows_f, d_.acc, d_.R, &d_.chi2S, &d_.chi2S_cap);
+                        max_rows_f, d_.acc, d_.R, &d_.chi2S, &d_.chi2S_cap, mode == 1);
     }
     if (tsdump) {  // synchronous copy-back: debug runs only (the chain loses its overlap)
       std::vector<long long> h(16 * (size_t)nf);
@@ -389,6 +393,7 @@ int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, s
     }
     sc.Tall = d_.Tall;
     sc.ldt = d_.ldh;
+    if (it.t_kmask) sc.kmask_tile = it.t_kmask + 2 * b.feats.size();
     {
       KScope ks(&kprof_, KC_EKF);
       launch_ekf_update(d_.stream, d_.P, d_.ldp, N_, d_.H, d_.ldh, m, n, b.hidx_dev, d_.H + n, d_.ldh, s2, sc);
@@ -450,6 +455,25 @@ int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, s
       const VarP &lm = slam_.at(it->fv[i]->featid);
       add_feature(this, it->fv[i], 1, lm->rep, o_, b.cams, b.slot_of_time, b.clones, b.feats, b.meas, b.vars, b.rows,
                   lm.get(), lm_canon[i]);
+    }
+    // the k-step masks (kernels.h DBatchParams::kmask): a feature's rows of H are non-zero only in the columns of
+    // its variables; n_canon < 512 (k_feature's limit), so 128 steps of 4 columns
+    if (!(slam_seven_parts() & kSevenDense) && b.n_canon < 512) {
+      const size_t nf = b.feats.size(), nt = ((size_t)b.rows + 15) / 16;
+      b.kmask.assign(2 * (nf + nt), 0ull);
+      for (size_t i = 0; i < nf; i++) {
+        const DFeat &F = b.feats[i];
+        unsigned long long *fm = &b.kmask[2 * i];
+        for (int v = F.var_off; v < F.var_off + F.nvar; v++) {
+          const DVar &dv = b.vars[v];
+          if (dv.canon < 0) continue;
+          for (int c = dv.canon; c < dv.canon + dv.size; c++) fm[(c >> 2) >> 6] |= 1ull << ((c >> 2) & 63);
+        }
+        for (int t = F.row_off / 16; t <= (F.row_off + 2 * F.nmeas - 1) / 16 && 2 * F.nmeas > 0; t++) {
+          b.kmask[2 * (nf + t)] |= fm[0];
+          b.kmask[2 * (nf + t) + 1] |= fm[1];
+        }
+      }
     }
     slam_items.push_back(it.get());
     items.push_back(std::move(it));

@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdlib>
+#include <cstring>
 
 #include "hp_math.h"
 #include "kprof.h"
@@ -97,7 +99,29 @@ struct DBatchParams {
   const DFeatOut *tri_in;
   const double *xv;
   int *gate_out;
+  // optional (SLAM chunks): per feature f the 128-bit mask kmask[2 f], kmask[2 f + 1] of the 4-wide k-steps (step s:
+  // canonical columns 4 s .. 4 s + 3) in which its rows of H_all can be non-zero, from the feature's variables
+  // (DVar::canon, size); followed by one such mask per 16-row tile of the batch's stacked rows, the OR of the
+  // features with rows in the tile.  The products over k visit only the set steps (dense_lds.h tile_chain_masked)
+  const unsigned long long *kmask;
 };
+
+// A/B switch, read once: UVIO_HP_SLAM_SEVEN=1 restores the seven-launch SLAM chunk with dense k-chains (k_feature,
+// k_gemm_HPg, k_chi2, k_ekf_MS, k_ekf_fact, k_ekf_WP, k_chain_apply) in place of the six-launch one (k_feature,
+// k_chi2_small, k_ekf_MS, k_ekf_fact, k_ekf_WP, k_chain_apply) whose products over k skip the structurally zero
+// steps.  Both form every value with the same expressions in the same order.  For per-step measurements the value
+// "gate" restores only the two-launch gate and "dense" only the dense k-chains (no k-step masks).
+constexpr int kSevenGate = 1, kSevenDense = 2;
+inline int slam_seven_parts() {
+  static const int v = [] {
+    const char *e = std::getenv("UVIO_HP_SLAM_SEVEN");
+    if (!e) return 0;
+    if (!std::strcmp(e, "gate")) return kSevenGate;
+    if (!std::strcmp(e, "dense")) return kSevenDense;
+    return kSevenGate | kSevenDense;
+  }();
+  return v;
+}
 
 // ---- launch wrappers (all asynchronous on `s`) ----
 // EKFPropagation (StateHelper.cpp:36-114) for a contiguous new block [s0, s0+p) with old index list
@@ -120,17 +144,21 @@ void launch_marginalize_multi(hipStream_t s, const double *P, double *Pout, int 
 void launch_check_diag(hipStream_t s, const double *P, int ld, int N, int *neg);
 
 // MSCKF / SLAM per-feature linearization: triangulation (+LM), Jacobian, nullspace, chi2, rows to H_all
+// zero (optional): set to 0 (the accepted-feature count of the batch's gate, which k_chi2_small only adds to)
 void launch_feature_linearize(hipStream_t s, const DBatchParams &bp, const DFeat *feats, const DMeas *meas,
                               const DVar *vars, const DClone *clones, const DCam *cams, const double *P,
-                              const double *chi2_table, double *H_all, DFeatOut *out, int max_meas, int max_nf);
+                              const double *chi2_table, double *H_all, DFeatOut *out, int max_meas, int max_nf,
+                              int *zero = nullptr);
 // batched chi2 gate (kernels_chi2.hip): T = H_all P[hidx, hidx], per-feature S / LDL^T / chi2;
 // rejected MSCKF / SLAM features get zero rows.  T_all: like H_all.
 // sbuf / sbuf_cap: the engine's buffer for the per-feature S of features too large for k_chi2's LDS staging
 // (formed by k_chi2_S over many CUs, grown here on demand); nullptr: k_chi2 forms S from global memory itself
+// small_gate: every feature is mode 1 and acc_count is already zero (launch_feature_linearize's zero): with
+// max_rows_f <= 16 the gate is the single launch k_chi2_small
 void launch_chi2_batch(hipStream_t s, const DBatchParams &bp, const DFeat *feats, const double *P, const int *hidx,
                        double *H_all, int m, double *T_all, const double *chi2_table, DFeatOut *out, int max_rows_f,
                        int *acc_count, double *pcan = nullptr,  // pcan: n^2 scratch for the gathered P_can
-                       double **sbuf = nullptr, size_t *sbuf_cap = nullptr);
+                       double **sbuf = nullptr, size_t *sbuf_cap = nullptr, bool small_gate = false);
 size_t feature_lds_bytes(int max_meas, int max_nf);
 
 // Compression: G = A^T A over rows of A = H_all (m x (n+1), ld = ldh), partials then Cholesky ->
@@ -190,6 +218,8 @@ struct EkfScratch {
   const double *Tall = nullptr;
   int ldt = 0;
   double *M3 = nullptr;  // the delayed-init candidate's initialize_invertible M (N x 3)
+  // optional, with Tall: the k-step mask of every 16-row tile of H (DBatchParams::kmask's second table)
+  const unsigned long long *kmask_tile = nullptr;
 };
 // W (N x r, ld r) = M L^-T for lower-triangular L (r x r, ld ldl); M row-major (ldm) or, with hidx, the
 // columns P[:, hidx] of P (ldm = ldp).  Dinv: scratch as in EkfScratch.

@@ -452,11 +452,147 @@ __global__ void __launch_bounds__(kChi2Threads) k_chi2(DBatchParams bp, const DF
   }
 }
 
+// The whole gate of a batch of small mode-1 features (a SLAM chunk: 2 or 4 rows per feature, at most 16) in one
+// launch instead of k_gemm_HPg + k_chi2<1>: one workgroup per feature, which
+//   * stages the column map and the feature's H rows in LDS,
+//   * forms its rows of T = H P_can padded to one 16-row tile, a wave per 16-column tile, with k_gemm_HPg's
+//     chain (ascending 4-wide MFMA steps over k, P gathered in the operand loads).  An element's chain does not
+//     depend on the rows that share its tile, and the zero-operand steps k_gemm_HPg appends past n add +0 to an
+//     accumulator that is never -0 (it starts at +0), so T is bit-identical.  The rows go to T_all (k_ekf_MS
+//     reads them) and stay in LDS for S,
+//   * S_f = T_f H_f^T + s2 I on one tile (tile_chain<16> from LDS, k_chi2's expression) with the residual row,
+//     and the same ldl_wave_inv<1> call as k_chi2<1> (R + 1 <= 17 rows: one panel on wave 0),
+//   * chi2: k_chi2 sums per-thread strided partials through a binary tree over 512 slots of which only the first
+//     R <= 16 are non-zero; every level above 16 adds +0 to a partial that is never -0 (0.0 + d y^2), and the
+//     levels from 16 down pair slot t with slot t + w.  The shuffle tree below over lanes 0 .. 63 of wave 0 does
+//     the same additions in the same order, so the sum is bit-identical.
+// With the batch's k-step masks (bp.kmask, kernels.h) both chains visit only the steps in which the feature's H rows
+// can be non-zero (dense_lds.h tile_chain_masked: the same values): about 45 of the chunk's ~230 columns, one round
+// trip of loads per tile instead of four.
+// The outcome (threshold, status, rows, zeroed rows of a rejected feature, the accepted count) is k_chi2's.  The
+// accepted count must be zero before this launch: the batch's k_feature zeroes it (launch_feature_linearize).
+constexpr int kGateMaxRows = 16;
+__global__ void __launch_bounds__(1024) k_chi2_small(DBatchParams bp, const DFeat *__restrict__ feats,
+                                                     const double *__restrict__ P, const int *__restrict__ hidx,
+                                                     double *__restrict__ H_all, double *__restrict__ T_all,
+                                                     const double *__restrict__ chi2_table, DFeatOut *__restrict__ out,
+                                                     int *acc_count) {
+  extern __shared__ double lds[];
+  __shared__ int st;
+  const int f = blockIdx.x;
+  long long *tsp = bp.dbg_ts ? bp.dbg_ts + (size_t)f * 16 + 8 : nullptr;  // debug phase stamps
+#define CHI2_TS(k) \
+  if (tsp && threadIdx.x == 0) tsp[k] = clock64();
+  CHI2_TS(0)
+  const DFeat F = feats[f];
+  const DFeatOut o = out[f];
+  const int n = bp.n_canon, ldh = bp.ldh, ldl = n | 1;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, nw = blockDim.x >> 6, r16 = lane & 15, kq = lane >> 4;
+  const int rows = min(2 * F.nmeas, kGateMaxRows);  // the feature's rows of H_all (k_feature writes all of them)
+  double *Hl = lds, *Tl = Hl + (size_t)kGateMaxRows * ldl;
+  double *S = Tl + (size_t)kGateMaxRows * ldl;  // (R + 1) x (R | 1), R <= 16
+  double *Dd = S + (kGateMaxRows + 1) * (kGateMaxRows | 1);
+  int *hs = (int *)(Dd + kGateMaxRows);
+  double *Hg = H_all + (size_t)F.row_off * ldh, *Tg = T_all + (size_t)F.row_off * ldh;
+  for (int e = tid; e < n; e += blockDim.x) hs[e] = hidx[e];
+  staged_copy(
+      rows * n, [&](int e) { return Hg[(size_t)(e / n) * ldh + e % n]; },
+      [&](int e, double v) { Hl[(size_t)(e / n) * ldl + e % n] = v; });
+  // the k-steps in which the feature's rows of H can be non-zero (both products below have H_f as an operand)
+  const bool masked = bp.kmask != nullptr;
+  const unsigned long long m0 = masked ? kmask_uniform(bp.kmask[2 * f]) : 0, m1 = masked ? kmask_uniform(bp.kmask[2 * f + 1]) : 0;
+  __syncthreads();
+  // T_f: column tile t of the feature's (padded) 16-row tile
+  for (int t = wid; t < (n + 15) / 16; t += nw) {
+    const int bcol = 16 * t + r16;
+    const bool ain = r16 < rows, bin = bcol < n;
+    const double *Pc = P + (bin ? hs[bcol] : 0);
+    dbl4 acc = {0.0, 0.0, 0.0, 0.0};
+    auto la = [&](int k) { return ain ? Hl[(size_t)r16 * ldl + k] : 0.0; };
+    auto lb = [&](int k) { return bin ? Pc[(size_t)hs[k] * bp.ldp] : 0.0; };
+    acc = masked ? tile_chain_masked<16>(m0, m1, n, kq, la, lb, acc) : tile_chain<16>(0, n, kq, la, lb, acc);
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const int row = kq + 4 * q, col = 16 * t + r16;
+      if (row < rows && col < n) {
+        Tg[(size_t)row * ldh + col] = acc[q];
+        Tl[(size_t)row * ldl + col] = acc[q];
+      }
+    }
+  }
+  if (o.status != 0 || o.rows <= 0) return;  // (uniform) not linearized: no gate, as in k_chi2
+  const int R = o.rows, ldS = R | 1;         // mode 1: every row is a chi2 row
+  __syncthreads();
+  if (wid == 0) {
+    const bool av = r16 < R;
+    dbl4 acc = {0.0, 0.0, 0.0, 0.0};
+    auto la = [&](int k) { return (av && k < n) ? Tl[(size_t)r16 * ldl + k] : 0.0; };
+    auto lb = [&](int k) { return (av && k < n) ? Hl[(size_t)r16 * ldl + k] : 0.0; };
+    acc = masked ? tile_chain_masked<16>(m0, m1, n, kq, la, lb, acc) : tile_chain<16>(0, n, kq, la, lb, acc);
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const int i = kq + 4 * q, j = r16;
+      if (i < R && j <= i) S[i * ldS + j] = acc[q] + (i == j ? bp.sigma_pix_sq : 0.0);
+    }
+    if (lane < R) S[R * ldS + lane] = Hg[(size_t)lane * ldh + n];
+  }
+  __syncthreads();
+  CHI2_TS(1)
+  ldl_wave_inv<1>(S, SqLayout{ldS}, R, R + 1, Dd, false);
+  CHI2_TS(2)
+  if (wid == 0) {
+    double c2 = 0.0;
+    if (lane < R) {
+      const double y = S[R * ldS + lane];
+      c2 += Dd[lane] * (y * y);
+    }
+    for (int w = 32; w > 0; w >>= 1) c2 += __shfl_down(c2, w, 64);
+    if (lane == 0) {
+      const double thr = chi2_table[min(R, 999)];
+      const int reject = c2 > bp.chi2_mult * thr;
+      out[f].chi2 = c2;
+      if (reject) {
+        out[f].status = 3;
+        out[f].rows = 0;
+      } else if (acc_count) {
+        atomicAdd(acc_count, 1);
+      }
+      st = reject;
+    }
+  }
+  CHI2_TS(3)
+#undef CHI2_TS
+  __syncthreads();
+  if (st) {
+    // the rejected feature's rows of H_all and of T = H_all P_can (the direct update's S reuses T)
+    for (int e = tid; e < o.rows * (n + 1); e += blockDim.x) {
+      const int i = e / (n + 1), j = e - i * (n + 1);
+      Hg[(size_t)i * ldh + j] = 0.0;
+      if (j < n) Tg[(size_t)i * ldh + j] = 0.0;
+    }
+  }
+}
+static size_t chi2_small_lds_bytes(int n) {
+  return ((size_t)2 * kGateMaxRows * (n | 1) + (kGateMaxRows + 1) * (kGateMaxRows | 1) + kGateMaxRows) * sizeof(double) +
+         (size_t)n * sizeof(int);
+}
+
 void launch_chi2_batch(hipStream_t s, const DBatchParams &bp, const DFeat *feats, const double *P, const int *hidx,
                        double *H_all, int m, double *T_all, const double *chi2_table, DFeatOut *out, int max_rows_f,
-                       int *acc_count, double *pcan, double **sbuf, size_t *sbuf_cap) {
+                       int *acc_count, double *pcan, double **sbuf, size_t *sbuf_cap, bool small_gate) {
   if (bp.nfeat <= 0 || m <= 0) return;
   const int n = bp.n_canon;
+  if (small_gate && max_rows_f <= kGateMaxRows && !(slam_seven_parts() & kSevenGate)) {
+    static int granted = -1;
+    if (granted < 0) granted = set_dyn_lds((const void *)k_chi2_small, kMaxDynLds);
+    const size_t bytes = chi2_small_lds_bytes(n);
+    if (bytes > 64 * 1024 && (int)bytes > granted)
+      throw std::runtime_error("k_chi2_small needs " + std::to_string(bytes) + " B of LDS, granted " + std::to_string(granted));
+    const int waves = std::min(16, std::max(2, (n + 15) / 16));  // a wave per column tile of T; ldl_wave_inv needs >= 2
+    hipLaunchKernelGGL(k_chi2_small, dim3(bp.nfeat), dim3(64 * waves), bytes, s, bp, feats, P, hidx, H_all, T_all,
+                       chi2_table, out, acc_count);
+    return;
+  }
   if (m >= 4096) {  // enough 64 x 64 tiles to fill the 256 CUs
     if (pcan)
       hipLaunchKernelGGL(k_gather_pcan, dim3((n * n + 255) / 256), dim3(256), 0, s, P, bp.ldp, hidx, n, pcan);

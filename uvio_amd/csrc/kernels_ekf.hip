@@ -28,12 +28,16 @@ namespace uvhp {
 
 // ---------------------------------------------------------------------------------------------------
 // K1: M (blocks 0 .. nbM-1) and S_up (blocks nbM .. nbM + ceil(r/16) - 1; none when Sup is null)
+// km (optional, with Tall: a SLAM chunk): the k-step mask of every 16-row tile of H (kernels.h DBatchParams::kmask).
+// Column tile t of M and the S tile pairs (a, b) have H's row tile t / a as an operand, so their chains visit only
+// its set steps (dense_lds.h tile_chain_masked: the same values).
 constexpr int kMSThreads = 512;  // 8 waves: one M column tile / one S tile pair per wave at cfg2's r ~ 100
 __global__ void __launch_bounds__(kMSThreads) k_ekf_MS(const double *__restrict__ P, int ldp, int N,
                                                 const double *__restrict__ H, int ldh, int r, int n,
                                                 const int *__restrict__ hidx, double s2, double *__restrict__ M,
                                                 double *__restrict__ Sup, int nbM, int *zero,
-                                                const double *__restrict__ Tall, int ldt) {
+                                                const double *__restrict__ Tall, int ldt,
+                                                const unsigned long long *__restrict__ km) {
   extern __shared__ double sh[];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int r16 = lane & 15, kq = lane >> 4;
@@ -59,8 +63,12 @@ __global__ void __launch_bounds__(kMSThreads) k_ekf_MS(const double *__restrict_
       const double *Hr = H + (size_t)min(jr, r - 1) * ldh;
       const bool jv = jr < r;
       dbl4 acc = {0.0, 0.0, 0.0, 0.0};
-      acc = tile_chain<16>(
-          0, n, kq, [&](int k) { return Ps[r16 * lds + k]; }, [&](int k) { return jv ? Hr[k] : 0.0; }, acc);
+      auto la = [&](int k) { return Ps[r16 * lds + k]; };
+      auto lb = [&](int k) { return jv ? Hr[k] : 0.0; };
+      if (km)
+        acc = tile_chain_masked<16>(kmask_uniform(km[2 * t]), kmask_uniform(km[2 * t + 1]), n, kq, la, lb, acc);
+      else
+        acc = tile_chain<16>(0, n, kq, la, lb, acc);
 #pragma unroll
       for (int q = 0; q < 4; q++) {
         const int row = i0 + kq + 4 * q, col = j0 + r16;
@@ -94,9 +102,12 @@ __global__ void __launch_bounds__(kMSThreads) k_ekf_MS(const double *__restrict_
     const double *Tb = gath ? Tall + min(br, r - 1) : Tall + (size_t)min(br, r - 1) * ldt;
     const bool av = ar < r, bv = br < r;
     dbl4 acc = {0.0, 0.0, 0.0, 0.0};
-    acc = tile_chain<16>(
-        0, n, kq, [&](int k) { return av ? Ha[k] : 0.0; },
-        [&](int k) { return bv ? (gath ? Tb[(size_t)hs[k] * r] : Tb[k]) : 0.0; }, acc);
+    auto la = [&](int k) { return av ? Ha[k] : 0.0; };
+    auto lb = [&](int k) { return bv ? (gath ? Tb[(size_t)hs[k] * r] : Tb[k]) : 0.0; };
+    if (km)
+      acc = tile_chain_masked<16>(kmask_uniform(km[2 * at]), kmask_uniform(km[2 * at + 1]), n, kq, la, lb, acc);
+    else
+      acc = tile_chain<16>(0, n, kq, la, lb, acc);
 #pragma unroll
     for (int q = 0; q < 4; q++) {
       const int row = 16 * at + kq + 4 * q, col = 16 * bt + r16;
@@ -496,7 +507,7 @@ void launch_ekf_M(hipStream_t s, const double *P, int ldp, int N, const double *
   if (lds > (size_t)kMaxDynLds) throw std::runtime_error("EKF update with too many columns for k_ekf_MS");
   const int nbM = (N + 15) / 16;
   hipLaunchKernelGGL(k_ekf_MS, dim3(nbM), dim3(kMSThreads), lds, s, P, ldp, N, H, ldh, r, n, hidx, 0.0, M,
-                     (double *)nullptr, nbM, zero, (const double *)nullptr, 0);
+                     (double *)nullptr, nbM, zero, (const double *)nullptr, 0, (const unsigned long long *)nullptr);
 }
 
 void launch_ekf_phaseA(hipStream_t s, const double *P, int ldp, int N, const double *H, int ldh, int r, int n,
@@ -516,21 +527,21 @@ void launch_ekf_phaseA(hipStream_t s, const double *P, int ldp, int N, const dou
   if (!Tall && !from_p) {
     const int nbG = (nt * (nt + 1) / 2 + wpb - 1) / wpb;
     hipLaunchKernelGGL(k_ekf_MS, dim3(nbM), dim3(kMSThreads), lds, s, P, ldp, N, H, ldh, r, n, hidx, sigma2, sc.M, Sup,
-                       nbM, sc.neg, (const double *)nullptr, 0);
+                       nbM, sc.neg, (const double *)nullptr, 0, (const unsigned long long *)nullptr);
     hipLaunchKernelGGL(k_ekf_MS, dim3(nbG), dim3(kMSThreads), lds, s, P, ldp, N, H, ldh, r, n, hidx, sigma2, sc.M, Sup,
-                       0, (int *)nullptr, (const double *)sc.M, -1);
+                       0, (int *)nullptr, (const double *)sc.M, -1, (const unsigned long long *)nullptr);
     return;
   }
   static const bool split = std::getenv("UVIO_HP_MS_SPLIT") != nullptr;  // diagnostic: M, then S, as two launches
   if (split) {
     hipLaunchKernelGGL(k_ekf_MS, dim3(nbM), dim3(kMSThreads), lds, s, P, ldp, N, H, ldh, r, n, hidx, sigma2, sc.M, Sup,
-                       nbM, sc.neg, Tall, sc.ldt);
+                       nbM, sc.neg, Tall, sc.ldt, sc.kmask_tile);
     hipLaunchKernelGGL(k_ekf_MS, dim3(nbS), dim3(kMSThreads), lds, s, P, ldp, N, H, ldh, r, n, hidx, sigma2, sc.M, Sup,
-                       0, (int *)nullptr, Tall, sc.ldt);
+                       0, (int *)nullptr, Tall, sc.ldt, sc.kmask_tile);
     return;
   }
   hipLaunchKernelGGL(k_ekf_MS, dim3(nbM + nbS), dim3(kMSThreads), lds, s, P, ldp, N, H, ldh, r, n, hidx, sigma2, sc.M, Sup,
-                     nbM, sc.neg, Tall, sc.ldt);
+                     nbM, sc.neg, Tall, sc.ldt, Tall ? sc.kmask_tile : (const unsigned long long *)nullptr);
 }
 
 static void launch_ekf_factor(hipStream_t s, int N, int r, const double *res, int res_stride, EkfScratch &sc) {

@@ -325,9 +325,10 @@ __global__ void __launch_bounds__(256) k_feature(DBatchParams bp, const DFeat *_
                                                  const DClone *__restrict__ clones, const DCam *__restrict__ cams,
                                                  const double *__restrict__ P, const double *__restrict__ chi2_table,
                                                  double *__restrict__ H_all, DFeatOut *__restrict__ out, int max_meas,
-                                                 int max_nf) {
+                                                 int max_nf, int *zero) {
   extern __shared__ double lds[];
   __shared__ FeatShared sh;
+  if (zero && blockIdx.x == 0 && threadIdx.x == 0) *zero = 0;  // the accepted-feature count of the batch's gate
   long long *tsp = bp.dbg_ts ? bp.dbg_ts + (size_t)blockIdx.x * 16 : nullptr;
 #define FEAT_TS(k) \
   if (tsp && threadIdx.x == 0) tsp[k] = clock64();
@@ -897,7 +898,8 @@ __global__ void __launch_bounds__(256) k_feature(DBatchParams bp, const DFeat *_
 
 void launch_feature_linearize(hipStream_t s, const DBatchParams &bp, const DFeat *feats, const DMeas *meas,
                               const DVar *vars, const DClone *clones, const DCam *cams, const double *P,
-                              const double *chi2_table, double *H_all, DFeatOut *out, int max_meas, int max_nf) {
+                              const double *chi2_table, double *H_all, DFeatOut *out, int max_meas, int max_nf,
+                              int *zero) {
   if (bp.nfeat <= 0) return;
   if (bp.n_canon >= 512 || max_meas > 64)  // canon2loc[512]; one lane per measurement
     throw std::runtime_error("k_feature: n_canon " + std::to_string(bp.n_canon) + " / measurements per feature " +
@@ -908,7 +910,7 @@ void launch_feature_linearize(hipStream_t s, const DBatchParams &bp, const DFeat
   if (bytes > 64 * 1024 && (int)bytes > granted)
     throw std::runtime_error("k_feature needs " + std::to_string(bytes) + " B of LDS, granted " + std::to_string(granted));
   hipLaunchKernelGGL(k_feature, dim3(bp.nfeat), dim3(256), bytes, s, bp, feats, meas, vars, clones, cams, P,
-                     chi2_table, H_all, out, max_meas, max_nf);
+                     chi2_table, H_all, out, max_meas, max_nf, zero);
 }
 
 // ---------------------------------------------------------------------------------------------------
