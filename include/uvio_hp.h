@@ -77,8 +77,11 @@ typedef struct {
   int max_slam_in_update;
   int max_msckf_in_update;
   int max_aruco_features;
-  int feat_rep_msckf;         /* LandmarkRepresentation (LandmarkRepresentation.h:38) */
-  int feat_rep_slam;
+  int feat_rep_msckf;         /* LandmarkRepresentation (LandmarkRepresentation.h:38), all six values 0-5; 5
+                               * (ANCHORED_INVERSE_DEPTH_SINGLE) is linearized as 4, as UpdaterMSCKF does */
+  int feat_rep_slam;          /* all six values 0-5; the state holds (x, y, z) for 0 and 2, (theta, phi, rho) for
+                               * 1 and 3, (alpha, beta, rho) for 4 and rho alone for 5 (a one-dimensional landmark
+                               * whose anchor bearing is kept in the handle); points: uvio_hp_get_features_slam */
   double dt_slam_delay;
   double gravity_mag;
   double calib_camimu_dt;
@@ -253,6 +256,13 @@ int uvio_hp_get_kernel_stats(uvio_hp_t *h, int flush, uvio_hp_kstat_t *out, int 
  * active_tracks_time.  *n receives the number of tracks (E_CAPACITY if > cap). */
 int uvio_hp_get_active_tracks(uvio_hp_t *h, double *t, uint64_t *ids, double *posinG, double *uvd, int *uvd_valid,
                               int cap, int *n);
+/* VioManager::get_features_SLAM (VioManagerHelper.cpp:417-438): every SLAM landmark of the state as a point in the
+ * global frame (3 per landmark), in the order of the landmarks' variables in the state vector; an anchored
+ * representation is transformed through its anchor clone and anchor camera.  With an inverse-depth feat_rep_slam
+ * the state vector holds (theta, phi, rho), (alpha, beta, rho) or a lone rho per landmark, not a point: read
+ * points here.
+ * *n receives the number of landmarks (E_CAPACITY if > cap). */
+int uvio_hp_get_features_slam(uvio_hp_t *h, uint64_t *ids, double *xyz_inG, int cap, int *n);
 /* number of clones and their timestamps (ascending) */
 int uvio_hp_get_clone_times(uvio_hp_t *h, double *out, int cap, int *n);
 /* TrackBase::get_last_obs / get_last_ids (TrackBase.h:137-148) for one camera: ids and raw (u, v) of
@@ -289,7 +299,9 @@ typedef struct {
 
 /* Overwrite the mean, the first estimates and the covariance (a state snapshot in the layout of
  * uvio_hp_get_state_vector / uvio_hp_get_fej_vector / uvio_hp_get_cov: same variables, len doubles,
- * N x N covariance with leading dimension ld).  Camera intrinsics follow the state (StateHelper.cpp:190-195). */
+ * N x N covariance with leading dimension ld).  Camera intrinsics follow the state (StateHelper.cpp:190-195).
+ * The anchor bearings of ANCHORED_INVERSE_DEPTH_SINGLE landmarks are not part of the vector: the handle keeps
+ * the ones it has, so a snapshot is only meaningful for the handle (or a copy of the run) it was taken from. */
 int uvio_hp_set_state(uvio_hp_t *h, const double *val, const double *fej, int len, const double *P, int N, int ld);
 /* Propagator::propagate_and_clone (Propagator.h:110) to t with the IMU readings fed so far */
 int uvio_hp_propagate_and_clone(uvio_hp_t *h, double t);

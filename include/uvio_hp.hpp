@@ -147,6 +147,17 @@ class Manager {
     x.resize(len);
     return x;
   }
+  // VioManager::get_features_SLAM: the SLAM landmarks as global points (3 per landmark) and, optionally, their ids
+  std::vector<double> features_slam(std::vector<uint64_t> *ids = nullptr) const {
+    int n = 0;
+    const int rc = uvio_hp_get_features_slam(h_, nullptr, nullptr, 0, &n);
+    if (rc != UVIO_HP_E_CAPACITY) check(rc);
+    std::vector<uint64_t> id((size_t)n);
+    std::vector<double> p((size_t)3 * n);
+    if (n > 0) check(uvio_hp_get_features_slam(h_, id.data(), p.data(), n, &n));
+    if (ids) *ids = id;
+    return p;
+  }
   uvio_hp_timing_t timing() const {
     uvio_hp_timing_t t{};
     check(uvio_hp_get_timing(h_, &t));

@@ -127,6 +127,7 @@ SIGNATURES = [
     ("get_timing", _I, [C.c_void_p, _P(Timing)]),
     ("get_clone_times", _I, [C.c_void_p, _P(_D), _I, _P(_I)]),
     ("get_active_tracks", _I, [C.c_void_p, _P(_D), _P(C.c_uint64), _P(_D), _P(_D), _P(_I), _I, _P(_I)]),
+    ("get_features_slam", _I, [C.c_void_p, _P(C.c_uint64), _P(_D), _I, _P(_I)]),
     ("set_kernel_timing", _I, [C.c_void_p, _I]),
     ("get_kernel_stats", _I, [C.c_void_p, _I, _P(KStat), _I, _P(_I)]),
     ("feed_camera_device", _I, [C.c_void_p, _D, _I, _P(_I), _P(C.c_void_p), _P(_I), _P(_P(C.c_uint8))]),

@@ -224,6 +224,14 @@ int uvio_hp_get_active_tracks(uvio_hp_t *h, double *t, uint64_t *ids, double *po
   })
 }
 
+int uvio_hp_get_features_slam(uvio_hp_t *h, uint64_t *ids, double *xyz_inG, int cap, int *n) {
+  if (!h || !n || cap < 0 || (cap > 0 && (!ids || !xyz_inG))) return UVIO_HP_E_ARG;
+  HP_GUARD(h, {
+    *n = h->e->get_features_slam(ids, xyz_inG, cap);
+    return *n <= cap ? 0 : UVIO_HP_E_CAPACITY;
+  })
+}
+
 int uvio_hp_set_kernel_timing(uvio_hp_t *h, int on) {
   if (!h) return UVIO_HP_E_ARG;
   if (on < 0) return UVIO_HP_E_ARG;

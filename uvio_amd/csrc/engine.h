@@ -39,6 +39,9 @@ struct Var {
   int rep = 0, anchor_cam = -1, unique_cam = -1, fail_count = 0;
   double anchor_time = -1;
   bool should_marg = false;
+  // ANCHORED_INVERSE_DEPTH_SINGLE: the anchor bearing p / z kept beside the one-dimensional state (Landmark.h:67-70);
+  // the state vector does not carry it
+  double uvn0[3] = {0, 0, 0}, uvn0_fej[3] = {0, 0, 0};
   // uwb anchor
   uint64_t anchor_id = 0;
   bool fixed = false;
@@ -690,6 +693,12 @@ class Engine {
 
  public:
   int get_active_tracks(double *t, uint64_t *ids, double *posinG, double *uvd, int *uvd_valid, int cap);
+  // a SLAM landmark's position in the global frame: an anchored representation goes through its anchor clone and
+  // camera (VioManagerHelper.cpp:422-435)
+  void landmark_in_global(const Var &lm, double *p_FinG) const;
+  // VioManager::get_features_SLAM (VioManagerHelper.cpp:417): every SLAM landmark, in the order of its variable in
+  // the state; returns their number (the first cap are written)
+  int get_features_slam(uint64_t *ids, double *xyz_inG, int cap) const;
 
  private:
   int slam_change_anchors();
@@ -748,8 +757,9 @@ class Engine {
   void replay_slam(ChainItem &it);
   void replay_delayed(ChainItem &tri, ChainItem &cand, int N0);
   double chain_times_[3] = {0, 0, 0};  // host seconds of the chain's MSCKF / SLAM / delayed-init parts
-  // 3-wide variables (zeroed landmark slots) at the given covariance offsets leave P in one compaction
-  void marginalize_slots(std::vector<int> slots);
+  // d-wide variables (zeroed landmark slots, d the landmark dimension) at the given covariance offsets leave P in
+  // one compaction
+  void marginalize_slots(std::vector<int> slots, int d = 3);
   void finish_batch(Batch &b, int mode, std::vector<DFeatOut> &outs);
 };
 

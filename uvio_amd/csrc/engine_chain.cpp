@@ -10,7 +10,8 @@
 //   * after every update k_chain_apply moves them by the update's dx with the host's own formulas
 //     (Var::update, quat_2_Rot; the same FP64 operations in the same order), gated by the update's acceptance;
 //   * the delayed initialization's batch triangulation feeds its per-candidate linearization on the device
-//     (DBatchParams::tri_in), each candidate's landmark goes into a fixed slot N0 + 3 j whose rows are zeroed
+//     (DBatchParams::tri_in), each candidate's landmark goes into a fixed slot N0 + d j (d: the landmark's
+//     dimension, 3 or 1) whose rows are zeroed
 //     when the candidate is rejected (zero rows of P make zero rows of every later M and K), and the host
 //     compacts the zeroed slots away afterwards in one gather.
 // Every update writes its dx into its own region of d_.chain; after ONE wait the host replays the updaters in
@@ -31,15 +32,15 @@ namespace uvhp {
 using clk = std::chrono::steady_clock;
 static double secs(clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); }
 
-void Engine::marginalize_slots(std::vector<int> slots) {
+void Engine::marginalize_slots(std::vector<int> slots, int d) {
   if (slots.empty()) return;
   std::sort(slots.begin(), slots.end());
   std::vector<int> src;
   src.reserve(N_);
   size_t k = 0;
   for (int i = 0; i < N_; i++) {
-    while (k < slots.size() && i >= slots[k] + 3) k++;
-    if (k < slots.size() && i >= slots[k] && i < slots[k] + 3) continue;
+    while (k < slots.size() && i >= slots[k] + d) k++;
+    if (k < slots.size() && i >= slots[k] && i < slots[k] + d) continue;
     src.push_back(i);
   }
   const int Nn = (int)src.size();
@@ -51,7 +52,7 @@ void Engine::marginalize_slots(std::vector<int> slots) {
   for (auto &v : vars_) {
     int shift = 0;
     for (int s : slots)
-      if (v->id > s) shift += 3;
+      if (v->id > s) shift += d;
     v->id -= shift;
   }
   N_ = Nn;
@@ -116,9 +117,11 @@ int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, s
       for (size_t i = c0; i < std::min(slam_upd.size(), c0 + chunk); i++) {
         FeatP &f = slam_upd[i];
         f->clean_old_measurements(clonetimes);
+        // a single inverse depth needs two measurements for its bearing projection; with one the feature only
+        // leaves the list (UpdaterSLAM.cpp:286-295)
         if (f->count() < 1)
           f->to_delete = true;
-        else
+        else if ((size_t)f->count() >= (slam_.at(f->featid)->rep == REP_ANCHORED_INVERSE_DEPTH_SINGLE ? 2u : 1u))
           keep.push_back(f);
       }
       all.insert(all.end(), keep.begin(), keep.end());
@@ -138,19 +141,15 @@ int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, s
     delayed.swap(keep);
   }
   if (up.empty() && slam_upd.empty() && delayed.empty()) return 0;
-  if (!up.empty() && o_.feat_rep_msckf != 0 && o_.feat_rep_msckf != 4)
-    throw HpError(UVIO_HP_E_CONFIG, "feat_rep_msckf: only GLOBAL_3D / ANCHORED_MSCKF_INVERSE_DEPTH are implemented");
-  const int rep_slam = o_.feat_rep_slam;
-  if (!delayed.empty() && rep_slam != 0 && rep_slam != 2 && rep_slam != 4)
-    throw HpError(UVIO_HP_E_CONFIG, "feat_rep_slam: representation not implemented");
-  for (auto &f : slam_upd) {
-    const VarP &lm = slam_.at(f->featid);
-    if (lm->rep != 0 && lm->rep != 2 && lm->rep != 4)
-      throw HpError(UVIO_HP_E_CONFIG, "feat_rep_slam: representation not implemented");
-  }
+  // the new landmarks' dimension d: 3, or 1 for the single inverse depth (whose delayed initialization exists only
+  // in the fused six-launch form)
+  const int rep_slam = o_.feat_rep_slam, d = landmark_rep_size(rep_slam);
+  if (!delayed.empty() && d == 1 && std::getenv("UVIO_HP_DI_UNFUSED"))
+    throw HpError(UVIO_HP_E_CONFIG, "UVIO_HP_DI_UNFUSED: the eight-launch delayed initialization has no d = 1 form "
+                                    "(feat_rep_slam: ANCHORED_INVERSE_DEPTH_SINGLE)");
   const int N0 = N_;
   const int K = (int)delayed.size();
-  if (N0 + 3 * K > d_.ldp) throw HpError(UVIO_HP_E_CAPACITY, "covariance capacity exceeded");
+  if (N0 + d * K > d_.ldp) throw HpError(UVIO_HP_E_CAPACITY, "covariance capacity exceeded");
 
   // ---- 1) host side first: the frame state blob and every batch's tables (the large MSCKF batches write
   // theirs straight into the staging ring while they are built)
@@ -469,7 +468,8 @@ int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, s
           if (dv.canon < 0) continue;
           for (int c = dv.canon; c < dv.canon + dv.size; c++) fm[(c >> 2) >> 6] |= 1ull << ((c >> 2) & 63);
         }
-        for (int t = F.row_off / 16; t <= (F.row_off + 2 * F.nmeas - 1) / 16 && 2 * F.nmeas > 0; t++) {
+        const int fr = feat_rows_out(F);
+        for (int t = F.row_off / 16; t <= (F.row_off + fr - 1) / 16 && fr > 0; t++) {
           b.kmask[2 * (nf + t)] |= fm[0];
           b.kmask[2 * (nf + t) + 1] |= fm[1];
         }
@@ -529,7 +529,7 @@ int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, s
     }
   }
   auto tl2 = clk::now();
-  // ---- 5) UpdaterSLAM::delayed_init: batch triangulation, then per candidate (fixed slot N0 + 3 j) the
+  // ---- 5) UpdaterSLAM::delayed_init: batch triangulation, then per candidate (fixed slot N0 + d j) the
   // linearization at the current state, initialize_invertible and the chi2-gated update of the other rows
   if (K > 0) {
     HPROF("chain.delayed");
@@ -554,7 +554,8 @@ int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, s
     cand->region = nreg;
     for (int j = 0; j < K; j++) {
       const DFeat &F = b.feats[j];
-      const int Ni = N0 + 3 * j, nup = 2 * F.nmeas - 3;
+      // d initializing rows and nup = 2 m - 3 update rows either way (rep 5: 2 m - 2 rows after the projection)
+      const int Ni = N0 + d * j, nup = 2 * F.nmeas - 3, Nn = Ni + d;
       bp.tri_in = tri_out + j;
       const char *tsdump = std::getenv("UVIO_HP_FEAT_TS");  // debug only: the candidate's phase cycle counts
       if (tsdump) {
@@ -585,15 +586,17 @@ int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, s
       static const bool di_unfused = std::getenv("UVIO_HP_DI_UNFUSED") != nullptr;  // the eight-launch chain (A/B)
       if (nup > 0 && !di_unfused) {
         sc.chi2_gate = d_.acc;
-        sc.chi2_thr = o_.slam_chi2_multipler * chi2_table_[std::min(2 * F.nmeas, 999)];
+        // StateHelper::initialize's threshold: the rows it was given (after the bearing projection for d = 1)
+        sc.chi2_thr = o_.slam_chi2_multipler * chi2_table_[std::min(feat_rows_out(F), 999)];
         sc.gate = nullptr;
         KScope ks(&kprof_, KC_EKF);
         launch_di_candidate(d_.stream, d_.P, d_.ldp, Ni, Hrow, d_.ldh, nup, n, cand->t_hidx, s2, sc, fo3 + j,
-                            sc.dx + Ni + 5, fr_cl, fr_cv, ncl, fr_cam, fr_camv, ncam, o_.do_calib_camera_pose,
-                            o_.do_calib_camera_intrinsics, sc.dx + Ni + 8);
-        kprof_.credit(KC_EKF, ekf_flops(Ni + 3, n, nup), ekf_bytes(Ni + 3, n, nup));
+                            sc.dx + Nn + 2, fr_cl, fr_cv, ncl, fr_cam, fr_camv, ncam, o_.do_calib_camera_pose,
+                            o_.do_calib_camera_intrinsics, sc.dx + Nn + 5, d);
+        kprof_.credit(KC_EKF, ekf_flops(Nn, n, nup), ekf_bytes(Nn, n, nup));
         continue;
       }
+      // (d = 3 from here: UVIO_HP_DI_UNFUSED with d = 1 was refused above, and nup >= 1 with two measurements)
       launch_init_invertible(d_.stream, d_.P, d_.ldp, Ni, Hrow, d_.ldh, n, cand->t_hidx, nullptr, s2, sc, fo3 + j, d_.acc,
                              sc.dx + Ni + 5);
       if (nup > 0) {
@@ -714,19 +717,20 @@ void Engine::replay_slam(ChainItem &it) {
 }
 
 // UpdaterSLAM::delayed_init: the batch triangulation's results (tri), then candidate by candidate (cand; slot
-// N0 + 3 j, region cand.region + j) the new landmark and its update's dx; the rejected candidates' zeroed slots
+// N0 + d j, region cand.region + j) the new landmark and its update's dx; the rejected candidates' zeroed slots
 // leave the covariance in one compaction
 void Engine::replay_delayed(ChainItem &tri, ChainItem &cand, int N0) {
-  const int K = (int)cand.fv.size(), rep_slam = o_.feat_rep_slam;
+  const int K = (int)cand.fv.size(), rep_slam = o_.feat_rep_slam, d = landmark_rep_size(rep_slam);
   std::vector<DFeatOut> touts, outs;
   finish_batch(tri.b, 2, touts);
   finish_batch(cand.b, 3, outs);
   last_upd_.clear();
-  N_ = N0 + 3 * K;
+  N_ = N0 + d * K;
   std::vector<int> dead;
   for (int j = 0; j < K; j++) {
     FeatP &f = cand.fv[j];
-    const int Ni = N0 + 3 * j, nup = 2 * cand.b.feats[j].nmeas - 3;
+    // the candidate's region: dx over Nn = Ni + d entries, then [chi2, -, resinit (d), -, accepted, neg] from Nn on
+    const int Ni = N0 + d * j, nup = 2 * cand.b.feats[j].nmeas - 3, Nn = Ni + d;
     f->to_delete = true;
     if (touts[j].status == 1 || touts[j].status == 2) {
       last_upd_.push_back(FeatDebug{f->featid, {0.0, 0.0, 0.0}, touts[j].status, 0.0});
@@ -739,36 +743,40 @@ void Engine::replay_delayed(ChainItem &tri, ChainItem &cand, int N0) {
     f->anchor_clone_timestamp = f->find((size_t)f->anchor_cam_id)->m.back().t;
     for (int k = 0; k < 3; k++) f->p_FinA[k] = touts[j].p_FinA[k], f->p_FinG[k] = touts[j].p_FinG[k];
     const double *base = d_.region_host(cand.region + j);
-    neg_check(base, Ni);
-    const bool accepted = base[Ni + 8] > 0.5;
+    if (base[Nn + 6] > 0.5) throw HpError(UVIO_HP_E_NUMERIC, "EKFUpdate: negative covariance diagonal");
+    const bool accepted = base[Nn + 5] > 0.5;
     last_upd_.push_back(FeatDebug{f->featid, {f->p_FinG[0], f->p_FinG[1], f->p_FinG[2]}, accepted ? 0 : 3,
-                                  nup > 0 ? base[Ni + 3] : 0.0});
+                                  nup > 0 ? base[Nn] : 0.0});
     frame_feats_.push_back({2, last_upd_.back()});
     if (!accepted) {
       dead.push_back(Ni);
       continue;
     }
-    VarP lm = std::make_shared<Var>(V_LANDMARK, 3, 3);
+    VarP lm = std::make_shared<Var>(V_LANDMARK, d, d);
     lm->featid = f->featid;
     lm->rep = rep_slam;
     lm->unique_cam = f->anchor_cam_id;
     lm->anchor_cam = f->anchor_cam_id;
     lm->anchor_time = f->anchor_clone_timestamp;
-    const bool relr = (rep_slam == 2 || rep_slam == 4);
+    const bool relr = landmark_rep_relative(rep_slam);
     lm->set_xyz(relr ? f->p_FinA : f->p_FinG, false);
     lm->set_xyz(relr ? f->p_FinA : f->p_FinG, true);
     lm->id = Ni;
     vars_.push_back(lm);
     double HLinv[9], dl[3];
-    inv3_cofactor(outs[j].HfR, HLinv);  // the device's formula: identical H_Linv
-    const double *resinit = base + Ni + 5;
-    for (int a = 0; a < 3; a++)
-      dl[a] = HLinv[3 * a] * resinit[0] + HLinv[3 * a + 1] * resinit[1] + HLinv[3 * a + 2] * resinit[2];
+    const double *resinit = base + Nn + 2;
+    if (d == 1) {
+      dl[0] = (1.0 / outs[j].HfR[0]) * resinit[0];  // the device's H_Linv (k_di_S): the scalar's reciprocal
+    } else {
+      inv3_cofactor(outs[j].HfR, HLinv);  // the device's formula: identical H_Linv
+      for (int a = 0; a < 3; a++)
+        dl[a] = HLinv[3 * a] * resinit[0] + HLinv[3 * a + 1] * resinit[1] + HLinv[3 * a + 2] * resinit[2];
+    }
     lm->update(dl);
     if (nup > 0) apply_dx(base);
     slam_.insert({f->featid, lm});
   }
-  marginalize_slots(dead);  // the rejected candidates' zeroed slots
+  marginalize_slots(dead, d);  // the rejected candidates' zeroed slots
 }
 
 }  // namespace uvhp

@@ -135,19 +135,7 @@ void Engine::retriangulate_active_tracks(double t, const std::vector<int> &camid
     const VarP &lm = kv.second;
     DRetriSlam d{};
     d.featid = lm->featid;
-    double p[3];
-    lm->xyz(false, p);
-    if (lm->rep == 2 || lm->rep == 3 || lm->rep == 4 || lm->rep == 5) {
-      double Ric[9], Rgi[9], d0[3], t1[3], t2[3];
-      quat_2_Rot(calib_pose_.at(lm->anchor_cam)->val, Ric);
-      const VarP &anc = clones_.at(lm->anchor_time);
-      quat_2_Rot(anc->val, Rgi);
-      for (int k = 0; k < 3; k++) d0[k] = p[k] - calib_pose_.at(lm->anchor_cam)->val[4 + k];
-      m3t_vec(Ric, d0, t1);
-      m3t_vec(Rgi, t1, t2);
-      for (int k = 0; k < 3; k++) p[k] = t2[k] + anc->val[4 + k];
-    }
-    for (int k = 0; k < 3; k++) d.pos[k] = p[k];
+    landmark_in_global(*lm, d.pos);
     sl.push_back(d);
   }
   // undistort_cv with the camera models as of now for the tracker's points, and for the simulated feed's when
@@ -215,6 +203,36 @@ void Engine::retri_flush() {
   rt_.nslam = job.nslam;
   rt_.time = rt_.pend_t;
   rt_.valid = true;
+}
+
+void Engine::landmark_in_global(const Var &lm, double *p) const {
+  lm.xyz(false, p);
+  if (!landmark_rep_relative(lm.rep)) return;
+  double Ric[9], Rgi[9], d0[3], t1[3], t2[3];
+  quat_2_Rot(calib_pose_.at(lm.anchor_cam)->val, Ric);
+  const VarP &anc = clones_.at(lm.anchor_time);
+  quat_2_Rot(anc->val, Rgi);
+  for (int k = 0; k < 3; k++) d0[k] = p[k] - calib_pose_.at(lm.anchor_cam)->val[4 + k];
+  m3t_vec(Ric, d0, t1);
+  m3t_vec(Rgi, t1, t2);
+  for (int k = 0; k < 3; k++) p[k] = t2[k] + anc->val[4 + k];
+}
+
+// The order is vars_', the order uvio_hp_get_state_vector writes the variables in (both walk vars_, State::_variables'
+// insertion order), so entry k here is the k-th landmark variable of that vector; the reference's own order, its
+// feature-id map's, carries no meaning.
+int Engine::get_features_slam(uint64_t *ids, double *xyz_inG, int cap) const {
+  int n = 0;
+  for (auto &v : vars_) {
+    if (v->kind != V_LANDMARK) continue;
+    if ((int)v->featid <= 4 * o_.max_aruco_features) continue;  // (ArUco corners: get_features_ARUCO's)
+    if (n < cap) {
+      ids[n] = v->featid;
+      landmark_in_global(*v, xyz_inG + 3 * n);
+    }
+    n++;
+  }
+  return n;
 }
 
 // VioManager::get_active_tracks (VioManager.h:114)

@@ -20,52 +20,10 @@ void Var::update(const double *dx) {
 }
 
 // Landmark::get_xyz (Landmark.cpp:26-63); representation ids of LandmarkRepresentation.h:38
-void Var::xyz(bool getfej, double *o) const {
-  const double *p = getfej ? fej : val;
-  switch (rep) {
-    case 0:
-    case 2:
-      o[0] = p[0]; o[1] = p[1]; o[2] = p[2];
-      break;
-    case 1:
-    case 3:
-      o[0] = (1 / p[2]) * cos(p[0]) * sin(p[1]);
-      o[1] = (1 / p[2]) * sin(p[0]) * sin(p[1]);
-      o[2] = (1 / p[2]) * cos(p[1]);
-      break;
-    case 4:
-      // reference quirk (Landmark.cpp:47-52): the fej value is ignored for this representation
-      o[0] = (1 / val[2]) * val[0];
-      o[1] = (1 / val[2]) * val[1];
-      o[2] = 1 / val[2];
-      break;
-    default:
-      o[0] = o[1] = o[2] = 0;
-  }
-}
+// (the shared statement of landmark_rep.h, which the device's landmark read uses too)
+void Var::xyz(bool getfej, double *o) const { landmark_get_xyz(rep, val, fej, uvn0, getfej, o); }
 void Var::set_xyz(const double *p, bool isfej) {
-  double *d = isfej ? fej : val;
-  switch (rep) {
-    case 0:
-    case 2:
-      d[0] = p[0]; d[1] = p[1]; d[2] = p[2];
-      break;
-    case 1:
-    case 3: {
-      double g_rho = 1 / sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
-      d[0] = atan2(p[1], p[0]);
-      d[1] = acos(g_rho * p[2]);
-      d[2] = g_rho;
-      break;
-    }
-    case 4:
-      d[0] = p[0] / p[2];
-      d[1] = p[1] / p[2];
-      d[2] = 1 / p[2];
-      break;
-    default:
-      break;
-  }
+  landmark_set_from_xyz(rep, p, isfej ? fej : val, isfej ? uvn0_fej : uvn0);
 }
 
 // ---- Feature (Feature.cpp:26-111) ----
@@ -98,10 +56,10 @@ Engine::Engine(const uvio_hp_options_t &o, int device) : o_(o), device_(device) 
   if (o_.use_aruco) throw HpError(UVIO_HP_E_CONFIG, "use_aruco: true (TrackAruco) is not implemented");
   if (o_.histogram_method < 0 || o_.histogram_method > 2)
     throw HpError(UVIO_HP_E_CONFIG, "histogram_method: 0 (NONE), 1 (HISTOGRAM) or 2 (CLAHE)");
-  if (o_.feat_rep_msckf != 0 && o_.feat_rep_msckf != 4)
-    throw HpError(UVIO_HP_E_CONFIG, "feat_rep_msckf: only GLOBAL_3D / ANCHORED_MSCKF_INVERSE_DEPTH are implemented");
-  if (o_.feat_rep_slam != 0 && o_.feat_rep_slam != 2 && o_.feat_rep_slam != 4)
-    throw HpError(UVIO_HP_E_CONFIG, "feat_rep_slam: only GLOBAL_3D / ANCHORED_3D / ANCHORED_MSCKF_INVERSE_DEPTH are implemented");
+  if (o_.feat_rep_msckf < 0 || o_.feat_rep_msckf > 5)
+    throw HpError(UVIO_HP_E_CONFIG, "feat_rep_msckf: unknown landmark representation");
+  if (o_.feat_rep_slam < 0 || o_.feat_rep_slam > 5)
+    throw HpError(UVIO_HP_E_CONFIG, "feat_rep_slam: unknown landmark representation");
   currid_ = 4 * (size_t)o_.max_aruco_features + 1;  // TrackBase::currid (TrackBase.cpp:34)
   int cur = 0;
   imu_ = mk(V_IMU, 15, 16);

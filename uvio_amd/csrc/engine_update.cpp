@@ -795,7 +795,10 @@ void add_feature(Engine *, const FeatP &f, int mode, int rep, const uvio_hp_opti
   DFeat F{};
   F.meas_off = (int)meas.size();
   F.var_off = (int)vars.size();
-  F.rep = rep;
+  // the updaters linearize the single inverse depth as the MSCKF inverse depth; in the SLAM updaters (not the MSCKF
+  // update, UpdaterMSCKF.cpp:181-183) its two bearing columns are then projected out (DFeat::single)
+  F.rep = (rep == REP_ANCHORED_INVERSE_DEPTH_SINGLE) ? REP_ANCHORED_MSCKF_INVERSE_DEPTH : rep;
+  F.single = (rep == REP_ANCHORED_INVERSE_DEPTH_SINGLE && mode != 0) ? 1 : 0;
   F.mode = mode;
   // anchor (FeatureInitializer.cpp:35-45): camera with most measurements (first max in map order),
   // anchor time = its last measurement
@@ -868,6 +871,8 @@ void add_feature(Engine *, const FeatP &f, int mode, int rep, const uvio_hp_opti
     landmark->xyz(false, p);
     landmark->xyz(true, pf);
     for (int k = 0; k < 3; k++) F.p_in[k] = p[k], F.p_in_fej[k] = pf[k];
+    if (landmark->rep == REP_ANCHORED_INVERSE_DEPTH_SINGLE)  // the anchor bearing goes with the feature (kernels.h)
+      for (int k = 0; k < 3; k++) F.p_in_fej[k] = landmark->uvn0[k];
   }
   F.nf = loc;
   F.nvar = (int)vars.size() - F.var_off;
@@ -890,7 +895,8 @@ void add_feature(Engine *, const FeatP &f, int mode, int rep, const uvio_hp_opti
   }
   F.nmeas = (int)meas.size() - F.meas_off;
   F.row_off = rows;
-  rows += (mode == 0) ? 2 * F.nmeas - 3 : 2 * F.nmeas;
+  F.rows = feat_rows_out(F);
+  rows += F.rows;
   feats.push_back(F);
 }
 
@@ -1125,6 +1131,18 @@ int Engine::slam_change_anchors() {
         }
       if (lm->rep == 2) {
         std::memcpy(Hf, RCG, sizeof(double) * 9);
+      } else if (lm->rep == 3) {  // ANCHORED_FULL_INVERSE_DEPTH (UpdaterHelper.cpp:124-150)
+        double a_rho = 1 / norm3(pFA), a_phi = acos(a_rho * pFA[2]), a_theta = atan2(pFA[1], pFA[0]);
+        double sth = sin(a_theta), cth = cos(a_theta), sph = sin(a_phi), cph = cos(a_phi), rho = a_rho;
+        double d[9] = {-(1.0 / rho) * sth * sph, (1.0 / rho) * cth * cph, -(1.0 / (rho * rho)) * cth * sph,
+                       (1.0 / rho) * cth * sph,  (1.0 / rho) * sth * cph, -(1.0 / (rho * rho)) * sth * sph,
+                       0.0, -(1.0 / rho) * sph, -(1.0 / (rho * rho)) * cph};
+        m3_mul(RCG, d, Hf);
+      } else if (lm->rep == 5) {  // ANCHORED_INVERSE_DEPTH_SINGLE: the 3 x 1 Jacobian (UpdaterHelper.cpp:175-186)
+        const double rho = 1.0 / pFA[2];
+        const double bear[3] = {rho * pFA[0], rho * pFA[1], rho * pFA[2]};
+        const double dr[3] = {-(1.0 / (rho * rho)) * bear[0], -(1.0 / (rho * rho)) * bear[1], -(1.0 / (rho * rho)) * bear[2]};
+        m3_vec(RCG, dr, Hf);
       } else {
         double alpha = pFA[0] / pFA[2], beta = pFA[1] / pFA[2], rho = 1 / pFA[2];
         double d[9] = {1.0 / rho, 0, -(1.0 / (rho * rho)) * alpha, 0, 1.0 / rho, -(1.0 / (rho * rho)) * beta, 0, 0,
@@ -1156,10 +1174,15 @@ int Engine::slam_change_anchors() {
     order.push_back({inew->id, 6});
     cur += 6;
     int c_lm = cur;
-    order.push_back({lm->id, 3});
-    cur += 3;
+    // the landmark's dimension pd: H_f is 3 x pd (row-major), H_f_new^-1 is pd x 3 and Phi has pd rows
+    const int pd = lm->size;
+    order.push_back({lm->id, pd});
+    cur += pd;
     double Hinv[9];
-    {
+    if (pd == 1) {  // the pseudo-inverse H^T / (H^T H) (UpdaterSLAM.cpp:610-618)
+      const double sq = dot3(Hf_new, Hf_new);
+      for (int k = 0; k < 3; k++) Hinv[k] = (1.0 / sq) * Hf_new[k];
+    } else {
       double *A = Hf_new;
       double det = A[0] * (A[4] * A[8] - A[5] * A[7]) - A[1] * (A[3] * A[8] - A[5] * A[6]) + A[2] * (A[3] * A[7] - A[4] * A[6]);
       Hinv[0] = (A[4] * A[8] - A[5] * A[7]) / det;
@@ -1172,9 +1195,9 @@ int Engine::slam_change_anchors() {
       Hinv[7] = (A[1] * A[6] - A[0] * A[7]) / det;
       Hinv[8] = (A[0] * A[4] - A[1] * A[3]) / det;
     }
-    std::vector<double> Phi((size_t)3 * cur, 0.0), Q(9, 0.0);
+    std::vector<double> Phi((size_t)pd * cur, 0.0);
     auto addblk = [&](int col, const double *H36, double sgn) {
-      for (int i = 0; i < 3; i++)
+      for (int i = 0; i < pd; i++)
         for (int j = 0; j < 6; j++) {
           double s = 0;
           for (int k = 0; k < 3; k++) s += Hinv[3 * i + k] * H36[6 * k + j];
@@ -1183,10 +1206,10 @@ int Engine::slam_change_anchors() {
     };
     addblk(c_old, Ha_old, 1.0);
     if (c_cal >= 0) addblk(c_cal, Hc_old, 1.0);
-    for (int i = 0; i < 3; i++)
-      for (int j = 0; j < 3; j++) {
+    for (int i = 0; i < pd; i++)
+      for (int j = 0; j < pd; j++) {
         double s = 0;
-        for (int k = 0; k < 3; k++) s += Hinv[3 * i + k] * Hf_old[3 * k + j];
+        for (int k = 0; k < 3; k++) s += Hinv[3 * i + k] * Hf_old[pd * k + j];
         Phi[(size_t)i * cur + c_lm + j] = s;
       }
     addblk(c_new, Ha_new, -1.0);
@@ -1194,10 +1217,10 @@ int Engine::slam_change_anchors() {
     std::vector<int> iold_ids;
     for (auto &o : order)
       for (int k = 0; k < o.second; k++) iold_ids.push_back(o.first + k);
-    if (b_rows.size() + 3 > 63 || b_iold.size() + iold_ids.size() > 256) flush();
+    if (b_rows.size() + pd > 63 || b_iold.size() + iold_ids.size() > 256) flush();
     for (int id : iold_ids)
       if (std::find(b_iold.begin(), b_iold.end(), id) == b_iold.end()) b_iold.push_back(id);
-    for (int i = 0; i < 3; i++) {
+    for (int i = 0; i < pd; i++) {
       b_rows.push_back(lm->id + i);
       std::vector<std::pair<int, double>> rowv;
       for (int c = 0; c < cur; c++)

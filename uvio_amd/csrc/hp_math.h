@@ -9,6 +9,8 @@
 
 #define HPD __host__ __device__ __forceinline__
 
+#include "landmark_rep.h"
+
 namespace uvhp {
 
 HPD void m3_mul(const double *A, const double *B, double *C) {

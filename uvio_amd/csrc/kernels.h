@@ -63,16 +63,22 @@ struct DFeat {
   int mode;             // 0 MSCKF (triangulate+refine+nullspace), 1 SLAM update (landmark in state),
                         // 2 delayed init (triangulate+refine, all rows), 3 delayed init at a given triangulation
   double p_in[3];       // SLAM: landmark xyz (value); MSCKF: unused
-  double p_in_fej[3];   // SLAM: landmark xyz (fej)
+  double p_in_fej[3];   // SLAM: landmark xyz (fej); single (whose get_xyz never reads the fej): the anchor bearing
   int lm_pid, lm_loc;   // SLAM: landmark covariance id / local col
-  int pad[2];
+  int single;           // SLAM updaters: an ANCHORED_INVERSE_DEPTH_SINGLE landmark, linearized as rep 4 (rep = 4,
+                        // UpdaterSLAM.cpp:162-165, 339-342) with the two bearing columns projected out (one column)
+  int rows;             // rows of H_all the feature owns (feat_rows_out below, set by the host)
 };
+
+// Rows of H_all a feature owns: the MSCKF projection drops 3, the single inverse depth's bearing projection (SLAM
+// updaters only; the MSCKF update just linearizes it as rep 4) drops 2
+HPD int feat_rows_out(const DFeat &F) { return 2 * F.nmeas - (F.mode == 0 ? 3 : (F.single ? 2 : 0)); }
 
 // Per-feature result
 struct DFeatOut {
   double p_FinA[3], p_FinG[3];
   double chi2;
-  double HfR[9];  // delayed init: the 3x3 upper block of H_f after the reflections (H_finit)
+  double HfR[9];  // delayed init: the 3x3 upper block of H_f after the reflections (H_finit); rep 5: HfR[0] alone
   int status;  // 0 accepted, 1 triangulation failed, 2 refine failed, 3 chi2 rejected
   int rows;    // rows written (accepted)
 };
@@ -266,16 +272,18 @@ struct DPoseVal {
 // (slot .. slot+2 over [0, Ntot)) are zeroed.
 void launch_chain_apply(hipStream_t s, const DFeatOut *fout, const int *gate, const int *neg, const double *dx,
                         DClone *clones, DPoseVal *cv, int ncl, DCam *cams, DPoseVal *camv, int ncam, int calib_ext,
-                        int calib_intr, double *xv, int Nx, double *P, int ldp, int Ntot, int slot, double *out);
+                        int calib_intr, double *xv, int Nx, double *P, int ldp, int Ntot, int slot, double *out,
+                        int d = 3);  // d: the slot's width, the landmark dimension (3, or 1 for rep 5)
 // One delayed-initialization candidate (StateHelper::initialize): initialize_invertible of the landmark into the
-// slot Ni (H_Linv from fout->HfR, rows Hrow[0..2]), the chi2-gated EKF update of the other nup rows (Hrow + 3,
+// slot Ni (H_Linv from fout->HfR, rows Hrow[0..d-1]), the chi2-gated EKF update of the other nup rows (Hrow + d,
 // residual in column n; sc.chi2_gate: in = the linearization gate, out = accepted; sc.chi2_thr), and the chain
 // step of launch_chain_apply (tables moved by dx, or the slot cleared; [accepted, neg] into out), as six launches.
-// resout receives the residual column of the three initializing rows.
+// resout receives the residual column of the d initializing rows.  d: the landmark dimension, 3 or 1 (the single
+// inverse depth: H_Linv = 1 / HfR[0]); a template parameter of the kernels, so d = 3 runs the code it always ran.
 void launch_di_candidate(hipStream_t s, double *P, int ldp, int Ni, const double *Hrow, int ldh, int nup, int n,
                          const int *hidx, double s2, EkfScratch &sc, const DFeatOut *fout, double *resout,
                          DClone *clones, DPoseVal *cv, int ncl, DCam *cams, DPoseVal *camv, int ncam, int calib_ext,
-                         int calib_intr, double *out);
+                         int calib_intr, double *out, int d = 3);
 double chi2_quantile95(int dof);
 
 // ---- VioManager::retriangulate_active_tracks (VioManagerHelper.cpp:190-388) on the device ----

@@ -488,7 +488,7 @@ __global__ void __launch_bounds__(1024) k_chi2_small(DBatchParams bp, const DFea
   const DFeatOut o = out[f];
   const int n = bp.n_canon, ldh = bp.ldh, ldl = n | 1;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, nw = blockDim.x >> 6, r16 = lane & 15, kq = lane >> 4;
-  const int rows = min(2 * F.nmeas, kGateMaxRows);  // the feature's rows of H_all (k_feature writes all of them)
+  const int rows = min(F.rows, kGateMaxRows);  // the feature's rows of H_all (k_feature writes all of them)
   double *Hl = lds, *Tl = Hl + (size_t)kGateMaxRows * ldl;
   double *S = Tl + (size_t)kGateMaxRows * ldl;  // (R + 1) x (R | 1), R <= 16
   double *Dd = S + (kGateMaxRows + 1) * (kGateMaxRows | 1);

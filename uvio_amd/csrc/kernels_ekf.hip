@@ -357,7 +357,9 @@ __device__ void chain_tables_apply(int t, const double *__restrict__ dx, DClone 
 }
 
 // Delayed-initialization chain step (kernels.h launch_chain_apply).  Block 0 updates the tables (one thread
-// per clone / camera) when the candidate was accepted; every block clears a rejected candidate's slot.
+// per clone / camera) when the candidate was accepted; every block clears a rejected candidate's slot of D rows and
+// columns (D: the landmark dimension, 3 or 1).
+template <int D>
 __global__ void __launch_bounds__(256) k_chain_apply(const DFeatOut *__restrict__ fout, const int *__restrict__ gate,
                                                      const int *__restrict__ neg, const double *__restrict__ dx,
                                                      DClone *__restrict__ clones, DPoseVal *__restrict__ cv, int ncl,
@@ -369,8 +371,8 @@ __global__ void __launch_bounds__(256) k_chain_apply(const DFeatOut *__restrict_
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (!acc) {
     if (slot >= 0)
-      for (int e = t; e < 3 * Ntot; e += gridDim.x * blockDim.x) {
-        const int i = e / 3, a = e - 3 * i;
+      for (int e = t; e < D * Ntot; e += gridDim.x * blockDim.x) {
+        const int i = e / D, a = e - D * i;
         P[(size_t)(slot + a) * ldp + i] = 0.0;
         P[(size_t)i * ldp + slot + a] = 0.0;
       }
@@ -386,11 +388,12 @@ __global__ void __launch_bounds__(256) k_chain_apply(const DFeatOut *__restrict_
 
 void launch_chain_apply(hipStream_t s, const DFeatOut *fout, const int *gate, const int *neg, const double *dx,
                         DClone *clones, DPoseVal *cv, int ncl, DCam *cams, DPoseVal *camv, int ncam, int calib_ext,
-                        int calib_intr, double *xv, int Nx, double *P, int ldp, int Ntot, int slot, double *out) {
+                        int calib_intr, double *xv, int Nx, double *P, int ldp, int Ntot, int slot, double *out, int d) {
   if (ncl + ncam > 256) throw std::runtime_error("update chain: more clones + cameras than one workgroup");
+  if (d != 3 && d != 1) throw std::runtime_error("update chain: landmark dimension " + std::to_string(d));
   const int nb = std::max(1, std::min(16, (std::max(3 * Ntot, Nx) + 255) / 256));
-  hipLaunchKernelGGL(k_chain_apply, dim3(nb), dim3(256), 0, s, fout, gate, neg, dx, clones, cv, ncl, cams, camv, ncam,
-                     calib_ext, calib_intr, xv, Nx, P, ldp, Ntot, slot, out);
+  hipLaunchKernelGGL(d == 3 ? k_chain_apply<3> : k_chain_apply<1>, dim3(nb), dim3(256), 0, s, fout, gate, neg, dx, clones,
+                     cv, ncl, cams, camv, ncam, calib_ext, calib_intr, xv, Nx, P, ldp, Ntot, slot, out);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -592,6 +595,7 @@ void launch_ekf_phaseB(hipStream_t s, double *P, int ldp, int N, int r, const do
 // stays behind UVIO_HP_DI_UNFUSED=1 for A/B runs; the 40-frame state digests of cfg3 and cfg3t are equal).
 // Measured and dropped: k_chain_apply folded into k_ekf_WP (the last workgroup to finish, after agent-scope
 // release / acquire fences around a completion counter, moving the tables): 22.8 us against 10.7 + 4.7 us.
+template <int D>
 __global__ void __launch_bounds__(kMSThreads) k_di_M(const double *__restrict__ P, int ldp, int Ni,
                                               const double *__restrict__ H, int ldh, int nup, int n,
                                               const int *__restrict__ hidx, double *__restrict__ M,
@@ -613,7 +617,7 @@ __global__ void __launch_bounds__(kMSThreads) k_di_M(const double *__restrict__ 
         Ps[i * lds + k] = v;
       });
   __syncthreads();
-  const double *Hup = H + 3 * (size_t)ldh;
+  const double *Hup = H + D * (size_t)ldh;
   const int nct = (nup + 15) / 16;
   for (int t = wid; t < nct; t += kMSThreads / 64) {
     const int j0 = 16 * t, jr = j0 + r16;
@@ -634,22 +638,31 @@ __global__ void __launch_bounds__(kMSThreads) k_di_M(const double *__restrict__ 
     for (int k = lane; k < n; k += 64) {
       const double p = Ps[i * lds + k];
 #pragma unroll
-      for (int b = 0; b < 3; b++) acc[b] = fma(p, H[(size_t)b * ldh + k], acc[b]);
+      for (int b = 0; b < D; b++) acc[b] = fma(p, H[(size_t)b * ldh + k], acc[b]);
     }
 #pragma unroll
     for (int b = 0; b < kSmallMRows; b++)
       for (int o = 32; o > 0; o >>= 1) acc[b] += __shfl_xor(acc[b], o, 64);
-    if (lane < 3) {
+    if (lane < D) {
       double v = acc[0];
 #pragma unroll
       for (int b = 1; b < kSmallMRows; b++)
         if (lane == b) v = acc[b];
-      M3[(size_t)(i0 + i) * 3 + lane] = v;
+      M3[(size_t)(i0 + i) * D + lane] = v;
     }
   }
 }
 
-constexpr int kDiInitThreads = 512;  // k_di_S's initialize_invertible blocks: (3 Ni + 511) / 512 of them
+constexpr int kDiInitThreads = 512;  // k_di_S's initialize_invertible blocks: (D Ni + 511) / 512 of them
+// H_Linv of the landmark's D x D H_finit (DFeatOut::HfR): the host's cofactor formula, or the scalar's reciprocal
+template <int D>
+__device__ __forceinline__ void di_hinv(const double *HfR, double *Hinv) {
+  if (D == 3)
+    inv3_cofactor(HfR, Hinv);
+  else
+    Hinv[0] = 1.0 / HfR[0];
+}
+template <int D>
 __global__ void __launch_bounds__(kMSThreads) k_di_S(double *__restrict__ P, int ldp, int Ni,
                                               const double *__restrict__ H, int ldh, int nup, int n,
                                               const int *__restrict__ hidx, double s2, double *__restrict__ M,
@@ -659,7 +672,7 @@ __global__ void __launch_bounds__(kMSThreads) k_di_S(double *__restrict__ P, int
   extern __shared__ double sh[];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int r16 = lane & 15, kq = lane >> 4;
-  const double *Hup = H + 3 * (size_t)ldh;
+  const double *Hup = H + D * (size_t)ldh;
   const int b = blockIdx.x;
   if (b < nbG) {
     // S_up[a][b] = H_a T_b^T with T[b][k] = M[hidx[k]][b] (k_ekf_MS, ldt < 0)
@@ -689,66 +702,67 @@ __global__ void __launch_bounds__(kMSThreads) k_di_S(double *__restrict__ P, int
     }
     return;
   }
-  __shared__ double Hinv[9], S3[9], PLL[9];
+  constexpr int DD = D * D;
+  __shared__ double Hinv[DD], S3[DD], PLL[DD];
   if (b < nbG + nbX) {
     // initialize_invertible (k_init_invertible with N = Ni: block xb takes the cross-covariance elements
     // xb * 512 ..; the first one also the 3x3 block)
     const int xb = b - nbG, t = threadIdx.x + xb * kDiInitThreads;
-    if (resout && xb == 0 && threadIdx.x < 3) resout[threadIdx.x] = H[(size_t)threadIdx.x * ldh + n];
+    if (resout && xb == 0 && threadIdx.x < D) resout[threadIdx.x] = H[(size_t)threadIdx.x * ldh + n];
     if (gate && *gate == 0) return;
-    if (threadIdx.x == 0) inv3_cofactor(fout->HfR, Hinv);
+    if (threadIdx.x == 0) di_hinv<D>(fout->HfR, Hinv);
     __syncthreads();
     if (xb == 0) {
-      __shared__ double part[9][28];
+      __shared__ double part[DD][28];
       const int e = threadIdx.x / 28, j = threadIdx.x % 28;
-      if (e < 9) {
-        const int a = e / 3, bb = e % 3;
+      if (e < DD) {
+        const int a = e / D, bb = e % D;
         double acc = 0.0;
-        for (int k = j; k < n; k += 28) acc += H[(size_t)a * ldh + k] * M3[(size_t)hidx[k] * 3 + bb];
+        for (int k = j; k < n; k += 28) acc += H[(size_t)a * ldh + k] * M3[(size_t)hidx[k] * D + bb];
         part[e][j] = acc;
       }
       __syncthreads();
-      if (threadIdx.x < 9) {
-        const int a = threadIdx.x / 3, bb = threadIdx.x % 3;
+      if (threadIdx.x < DD) {
+        const int a = threadIdx.x / D, bb = threadIdx.x % D;
         double acc = 0.0;
         for (int q = 0; q < 28; q++) acc += part[threadIdx.x][q];
         S3[threadIdx.x] = acc + (a == bb ? s2 : 0.0);
       }
       __syncthreads();
-      if (threadIdx.x < 9) {
-        const int a = threadIdx.x / 3, bb = threadIdx.x % 3;
+      if (threadIdx.x < DD) {
+        const int a = threadIdx.x / D, bb = threadIdx.x % D;
         double acc = 0.0;
-        for (int c = 0; c < 3; c++)
-          for (int e2 = 0; e2 < 3; e2++) {
-            const double sce = (c <= e2) ? S3[c * 3 + e2] : S3[e2 * 3 + c];
-            acc += Hinv[a * 3 + c] * sce * Hinv[bb * 3 + e2];
+        for (int c = 0; c < D; c++)
+          for (int e2 = 0; e2 < D; e2++) {
+            const double sce = (c <= e2) ? S3[c * D + e2] : S3[e2 * D + c];
+            acc += Hinv[a * D + c] * sce * Hinv[bb * D + e2];
           }
         PLL[threadIdx.x] = acc;
       }
     }
-    if (t < Ni * 3) {
-      const int i = t / 3, a = t % 3;
+    if (t < Ni * D) {
+      const int i = t / D, a = t % D;
       double acc = 0.0;
-      for (int bb = 0; bb < 3; bb++) acc += M3[(size_t)i * 3 + bb] * Hinv[a * 3 + bb];
+      for (int bb = 0; bb < D; bb++) acc += M3[(size_t)i * D + bb] * Hinv[a * D + bb];
       P[(size_t)i * ldp + Ni + a] = -acc;
       P[(size_t)(Ni + a) * ldp + i] = -acc;
     }
-    if (xb == 0 && threadIdx.x < 9) {
-      const int a = threadIdx.x / 3, bb = threadIdx.x % 3;
+    if (xb == 0 && threadIdx.x < DD) {
+      const int a = threadIdx.x / D, bb = threadIdx.x % D;
       P[(size_t)(Ni + a) * ldp + Ni + bb] = PLL[threadIdx.x];
     }
     return;
   }
-  // the landmark's rows Ni .. Ni+2 of M_up: P[Ni + a][hidx[k]] as initialize_invertible writes it, then the
-  // 16-row tiles of k_ekf_MS (only these three rows of the tile are stored)
+  // the landmark's rows Ni .. Ni+D-1 of M_up: P[Ni + a][hidx[k]] as initialize_invertible writes it, then the
+  // 16-row tiles of k_ekf_MS (only these D rows of the tile are stored)
   if (gate && *gate == 0) return;
-  double *Pl = sh;  // 3 x n
-  if (threadIdx.x == 0) inv3_cofactor(fout->HfR, Hinv);
+  double *Pl = sh;  // D x n
+  if (threadIdx.x == 0) di_hinv<D>(fout->HfR, Hinv);
   __syncthreads();
-  for (int e = threadIdx.x; e < 3 * n; e += blockDim.x) {
+  for (int e = threadIdx.x; e < D * n; e += blockDim.x) {
     const int a = e / n, k = e - a * n, i = hidx[k];
     double acc = 0.0;
-    for (int bb = 0; bb < 3; bb++) acc += M3[(size_t)i * 3 + bb] * Hinv[a * 3 + bb];
+    for (int bb = 0; bb < D; bb++) acc += M3[(size_t)i * D + bb] * Hinv[a * D + bb];
     Pl[e] = -acc;
   }
   __syncthreads();
@@ -756,16 +770,17 @@ __global__ void __launch_bounds__(kMSThreads) k_di_S(double *__restrict__ P, int
   for (int t = wid; t < nct; t += kMSThreads / 64) {
     const int j0 = 16 * t, jr = j0 + r16;
     const double *Hr = Hup + (size_t)min(jr, nup - 1) * ldh;
-    const bool jv = jr < nup, rv = r16 < 3;
+    const bool jv = jr < nup, rv = r16 < D;
     dbl4 acc = {0.0, 0.0, 0.0, 0.0};
     acc = tile_chain<16>(
         0, n, kq, [&](int k) { return rv ? Pl[r16 * n + k] : 0.0; }, [&](int k) { return jv ? Hr[k] : 0.0; }, acc);
     const int col = j0 + r16;
-    if (kq < 3 && col < nup) M[(size_t)(Ni + kq) * nup + col] = acc[0];
+    if (kq < D && col < nup) M[(size_t)(Ni + kq) * nup + col] = acc[0];
   }
 }
 
-void launch_di_candidate(hipStream_t s, double *P, int ldp, int Ni, const double *Hrow, int ldh, int nup, int n,
+template <int D>
+static void di_candidate(hipStream_t s, double *P, int ldp, int Ni, const double *Hrow, int ldh, int nup, int n,
                          const int *hidx, double s2, EkfScratch &sc, const DFeatOut *fout, double *resout,
                          DClone *clones, DPoseVal *cv, int ncl, DCam *cams, DPoseVal *camv, int ncam, int calib_ext,
                          int calib_intr, double *out) {
@@ -775,32 +790,46 @@ void launch_di_candidate(hipStream_t s, double *P, int ldp, int Ni, const double
   ensure_ekf_lds_attrs();
   static bool attrs = false;
   if (!attrs) {
-    if (set_dyn_lds((const void *)k_di_M, kMaxDynLds) < kMaxDynLds ||
-        set_dyn_lds((const void *)k_di_S, kMaxDynLds) < kMaxDynLds)
+    if (set_dyn_lds((const void *)k_di_M<D>, kMaxDynLds) < kMaxDynLds ||
+        set_dyn_lds((const void *)k_di_S<D>, kMaxDynLds) < kMaxDynLds)
       throw std::runtime_error("dynamic LDS limit not granted for a delayed-init kernel");
     attrs = true;
   }
   const size_t ldsM = (size_t)16 * (n | 1) * sizeof(double);
-  const size_t ldsS = std::max((size_t)n * sizeof(int), (size_t)3 * n * sizeof(double));
+  const size_t ldsS = std::max((size_t)n * sizeof(int), (size_t)D * n * sizeof(double));
   if (ldsM > (size_t)kMaxDynLds || ldsS > (size_t)kMaxDynLds)
     throw std::runtime_error("delayed-init candidate with too many columns");
-  const int N = Ni + 3;
+  const int N = Ni + D;
   {
-    hipLaunchKernelGGL(k_di_M, dim3((Ni + 15) / 16), dim3(kMSThreads), ldsM, s, P, ldp, Ni, Hrow, ldh, nup, n, hidx,
+    hipLaunchKernelGGL(k_di_M<D>, dim3((Ni + 15) / 16), dim3(kMSThreads), ldsM, s, P, ldp, Ni, Hrow, ldh, nup, n, hidx,
                        sc.M, sc.M3, sc.neg);
     const int nt = (nup + 15) / 16, wpb = kMSThreads / 64;
-    const int nbG = (nt * (nt + 1) / 2 + wpb - 1) / wpb, nbX = (3 * Ni + kDiInitThreads - 1) / kDiInitThreads;
+    const int nbG = (nt * (nt + 1) / 2 + wpb - 1) / wpb, nbX = (D * Ni + kDiInitThreads - 1) / kDiInitThreads;
     double *Sup = sc.S + 2 * (size_t)nup * nup;
-    hipLaunchKernelGGL(k_di_S, dim3(nbG + nbX + 1), dim3(kMSThreads), ldsS, s, P, ldp, Ni, Hrow, ldh, nup, n, hidx,
+    hipLaunchKernelGGL(k_di_S<D>, dim3(nbG + nbX + 1), dim3(kMSThreads), ldsS, s, P, ldp, Ni, Hrow, ldh, nup, n, hidx,
                        s2, sc.M, sc.M3, Sup, fout, sc.chi2_gate, resout, nbG, nbX);
-    launch_ekf_factor(s, N, nup, Hrow + 3 * (size_t)ldh + n, ldh, sc);
+    launch_ekf_factor(s, N, nup, Hrow + D * (size_t)ldh + n, ldh, sc);
     const int nb = (N + 15) / 16;
     const size_t lw = (size_t)(32 * (nup | 1) + 1024) * sizeof(double);
     hipLaunchKernelGGL(k_ekf_WP, dim3(nb * (nb + 1) / 2), dim3(256), lw, s, P, ldp, N, sc.M, nup, sc.S, sc.y, sc.dx,
                        sc.neg, sc.chi2_gate, nb);
   }
   launch_chain_apply(s, fout, sc.chi2_gate, sc.neg, sc.dx, clones, cv, ncl, cams, camv, ncam, calib_ext, calib_intr,
-                     nullptr, 0, P, ldp, N, Ni, out);
+                     nullptr, 0, P, ldp, N, Ni, out, D);
+}
+
+void launch_di_candidate(hipStream_t s, double *P, int ldp, int Ni, const double *Hrow, int ldh, int nup, int n,
+                         const int *hidx, double s2, EkfScratch &sc, const DFeatOut *fout, double *resout,
+                         DClone *clones, DPoseVal *cv, int ncl, DCam *cams, DPoseVal *camv, int ncam, int calib_ext,
+                         int calib_intr, double *out, int d) {
+  if (d == 3)
+    di_candidate<3>(s, P, ldp, Ni, Hrow, ldh, nup, n, hidx, s2, sc, fout, resout, clones, cv, ncl, cams, camv, ncam,
+                    calib_ext, calib_intr, out);
+  else if (d == 1)
+    di_candidate<1>(s, P, ldp, Ni, Hrow, ldh, nup, n, hidx, s2, sc, fout, resout, clones, cv, ncl, cams, camv, ncam,
+                    calib_ext, calib_intr, out);
+  else
+    throw std::runtime_error("delayed-init candidate: landmark dimension " + std::to_string(d));
 }
 
 void launch_ekf_update(hipStream_t s, double *P, int ldp, int N, const double *H, int ldh, int r, int n,

@@ -370,13 +370,19 @@ __global__ void __launch_bounds__(256) k_feature(DBatchParams bp, const DFeat *_
     }
     if (F.mode == 1 && bp.xv && F.lm_pid >= 0) {  // Landmark::get_xyz of the current value (Landmark.cpp:26-63)
       const double *v = bp.xv + F.lm_pid;
-      if (F.rep == 4) {
-        pin[0] = (1 / v[2]) * v[0];
-        pin[1] = (1 / v[2]) * v[1];
-        pin[2] = 1 / v[2];
+      // the shared statement (landmark_rep.h), with the representation a constant on the paths that have always
+      // been here, so their code stays what it was; the single inverse depth's anchor bearing is not in xv: it
+      // comes in p_in_fej (kernels.h DFeat)
+      if (F.single) {
+        landmark_get_xyz(5, v, v, F.p_in_fej, false, pin);
+        for (int k = 0; k < 3; k++) pinf[k] = pin[k];  // (no fej read either)
+      } else if (F.rep == 4) {
+        landmark_get_xyz(4, v, v, nullptr, false, pin);
         for (int k = 0; k < 3; k++) pinf[k] = pin[k];  // the reference ignores the fej value here
+      } else if (F.rep == 0 || F.rep == 2) {
+        landmark_get_xyz(0, v, v, nullptr, false, pin);
       } else {
-        for (int k = 0; k < 3; k++) pin[k] = v[k];
+        landmark_get_xyz(F.rep, v, v, nullptr, false, pin);
       }
     }
     for (int k = 0; k < 3; k++) {
@@ -613,6 +619,9 @@ __global__ void __launch_bounds__(256) k_feature(DBatchParams bp, const DFeat *_
     // representation Jacobian (UpdaterHelper.cpp:32-190) and anchor terms
     double dl[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};  // dpfg_dlambda
     double Hanc[18], Hcal[18];                   // 3x6 each
+    // Nothing reaches the F.rep == 5 cases of this section (one H_f column, the 3 x 1 Jacobian, rel): the host hands
+    // a single inverse depth over as rep 4 with DFeat::single (engine_update.cpp add_feature) and forms the anchor
+    // change's 3 x 1 Jacobian itself.  They stay so that the section is the code it was before DFeat::single.
     int ncolf = (F.rep == 5) ? 1 : 3;
     if (!rel) {
       for (int k = 0; k < 3; k++) {
@@ -781,8 +790,13 @@ __global__ void __launch_bounds__(256) k_feature(DBatchParams bp, const DFeat *_
         for (int j = 0; j < 8; j++) row[mm.lc_intr + j] = dzeta[8 * i + j];
       row[nf] = (i == 0) ? res0 : res1;
       // SLAM update: landmark columns hold H_f (UpdaterSLAM.cpp:355-358)
-      if (F.mode == 1)
-        for (int j = 0; j < ncolf; j++) row[F.lm_loc + j] = hf[j];
+      // the single inverse depth's one column is H_f's third; the bearing projection below reflects it with the row
+      if (F.mode == 1) {
+        if (F.single)
+          row[F.lm_loc] = hf[2];
+        else
+          for (int j = 0; j < ncolf; j++) row[F.lm_loc + j] = hf[j];
+      }
     }
   }
   __syncthreads();
@@ -793,8 +807,16 @@ __global__ void __launch_bounds__(256) k_feature(DBatchParams bp, const DFeat *_
   // [Hl | r] then takes all three in one read and one write pass per column: with w_c = v_c^T A,
   //   u_1 = b_1 w_1,  u_2 = b_2 (w_2 - g21 u_1),  u_3 = b_3 (w_3 - g31 u_1 - g32 u_2),  g_ab = v_a^T v_b,
   // H_3 H_2 H_1 A = A - v_1 u_1 - v_2 u_2 - v_3 u_3.
+  // Single inverse depth (DFeat::single; linearized as rep 4 above).  UpdaterSLAM.cpp:190-202, 366-377 project the
+  // two bearing columns of H_f out of [H_x | H_f(:, 2) | r] and drop two rows: the first two reflectors are that
+  // projection.  In the SLAM update (mode 1) the landmark's column, H_f's third, sits in Hl and is reflected with
+  // the rest, and the third reflector is switched off (v_3 = 0, beta_3 = 0); in the delayed initialization (mode 3)
+  // the third reflector is StateHelper::initialize's split of the remaining column (row 2 the initialization row,
+  // H_finit = Hf[2][2]).  Rows 0-1 are not written out.  The reference's Givens sequence gives the same rows up
+  // to an orthogonal change of row basis.
+  const bool single = F.single != 0;
   int r0 = 0;  // first output row in Hl
-  if (status0 == 0 && F.mode != 1) {
+  if (status0 == 0 && (F.mode != 1 || single)) {
     if (wave == 0) {
       for (int c = 0; c < 3; c++) {
         // v = x - alpha e_c over rows c..rows-1 (zero above)
@@ -821,6 +843,11 @@ __global__ void __launch_bounds__(256) k_feature(DBatchParams bp, const DFeat *_
           d = b * wave_sum(d);
           for (int i = c + lane; i < rows; i += 64) Hf[i * 3 + j] -= d * V[i * 3 + c];
         }
+        wave_sync();
+      }
+      if (F.mode == 1) {  // (single) the third reflector, formed above like the others, is not applied
+        for (int i = lane; i < rows; i += 64) V[i * 3 + 2] = 0.0;
+        if (lane == 0) sh.beta[2] = 0.0;
         wave_sync();
       }
       double g0 = 0.0, g1 = 0.0, g2 = 0.0;
@@ -857,7 +884,7 @@ __global__ void __launch_bounds__(256) k_feature(DBatchParams bp, const DFeat *_
   const int status = sh.status;  // 0 or a triangulation / refinement failure; chi2 is k_chi2's
   FEAT_TS(6)
   // ---- output rows (canonical dense columns; zeros when rejected) ----
-  const int out_r0 = (F.mode == 0) ? 3 : 0;
+  const int out_r0 = (F.mode == 0) ? 3 : single ? 2 : 0;  // (= 2 F.nmeas - feat_rows_out(F), kernels.h)
   const int nrows_out = max(rows - out_r0, 0);
   {
     // one wave per row, lanes over the canonical columns (n_canon + 1 <= 512: 8 column slots per lane,
@@ -887,6 +914,10 @@ __global__ void __launch_bounds__(256) k_feature(DBatchParams bp, const DFeat *_
     }
     o.chi2 = -1.0;
     for (int k = 0; k < 9; k++) o.HfR[k] = (F.mode >= 2 && status0 == 0) ? Hf[(k / 3) * 3 + (k % 3)] : 0.0;
+    if (single && F.mode >= 2 && status0 == 0) {  // the scalar H_finit first, nothing else
+      o.HfR[0] = Hf[2 * 3 + 2];
+      for (int k = 1; k < 9; k++) o.HfR[k] = 0.0;
+    }
     o.status = status;
     o.rows = status == 0 ? nrows_out : 0;
     out[f] = o;

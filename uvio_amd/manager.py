@@ -438,6 +438,20 @@ class VioManager:
         D = {int(ids[i]): uvd[i].copy() for i in range(k) if ok[i]}
         return t.value, P, D
 
+    def get_features_slam(self):
+        """VioManager::get_features_SLAM (VioManagerHelper.cpp:417): {featid: p_FinG} of every SLAM landmark, an
+        anchored representation transformed through its anchor clone and camera."""
+        n = C.c_int()
+        rc = self._call("get_features_slam", self._h, None, None, 0, C.byref(n))  # the count first
+        if rc != N.E_CAPACITY:
+            self._check(rc, "get_features_slam")
+        cap = max(n.value, 1)
+        ids = np.zeros(cap, dtype=np.uint64)
+        pos = np.zeros((cap, 3))
+        self._check(self._call("get_features_slam", self._h, ids.ctypes.data_as(C.POINTER(C.c_uint64)), _dp(pos), cap,
+                               C.byref(n)), "get_features_slam")
+        return {int(ids[i]): pos[i].copy() for i in range(n.value)}
+
     def get_clone_times(self):
         out = np.zeros(256)
         n = C.c_int()
