@@ -194,17 +194,3 @@ def test_updater_level_calls_representation(rep):
     assert moved >= nlm
     g.close()
 
-
-def test_unfused_delayed_init_refuses_single_inverse_depth(monkeypatch):
-    """UVIO_HP_DI_UNFUSED=1 (the eight-launch delayed initialization, an A/B switch) has no one-dimensional form:
-    with feat_rep_slam = ANCHORED_INVERSE_DEPTH_SINGLE the first delayed initialization fails with E_CONFIG instead
-    of giving another answer"""
-    import uvio_amd as U
-    monkeypatch.setenv("UVIO_HP_DI_UNFUSED", "1")
-    opts = U.load_options(EUROC, feat_rep_msckf=4, feat_rep_slam=5, **SLAM_KW)
-    g = U.VioManager(opts)
-    try:
-        with pytest.raises(RuntimeError, match="E_CONFIG.*UVIO_HP_DI_UNFUSED"):
-            _sim(opts, 30, spawn=80, frac_long=0.3).run(g, n_frames=30)
-    finally:
-        g.close()

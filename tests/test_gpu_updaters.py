@@ -222,6 +222,65 @@ def test_delayed_init_beyond_the_configured_landmark_count(euroc_yaml):
     g.close()
 
 
+def _stereo_cut(meas, which):
+    """the track's measurements at the stereo times (clone times at which both cameras saw it, ascending) with the
+    indices `which`: two measurements per time"""
+    times = sorted(set(m[1] for m in meas))
+    both = [t for t in times if len(set(m[0] for m in meas if m[1] == t)) == 2]
+    keep = set(both[i] for i in which) if both else set()
+    return [m for m in meas if m[1] in keep]
+
+
+@pytest.mark.parametrize("rep,d", [(4, 3), (5, 1)])
+def test_delayed_init_smallest_candidates(euroc_yaml, rep, d):
+    """The smallest candidates UpdaterSLAM::delayed_init can hand the update chain, in one call: a candidate of
+    exactly two measurements (both cameras at its last stereo clone time: 2 m - 3 = 1 update row beside the d
+    initializing rows), one of two stereo times (4 measurements, 5 update rows) and one full-length track, at
+    d = 3 (ANCHORED_MSCKF_INVERSE_DEPTH) and d = 1 (ANCHORED_INVERSE_DEPTH_SINGLE).
+
+    The short candidates are chosen with the oracle alone: a second oracle over the same stream adopts the
+    snapshot and takes the truncated candidates one at a time; the first one it initializes is used (most
+    two-measurement cuts fail the triangulation's baseline checks, and a rejected one leaves the oracle as it
+    was).  The one-row candidate goes first in the list, so the call sees it at the state it was probed at, and
+    the oracle must accept it there: the test cannot pass on rejected candidates alone.  Both representations have
+    such a candidate in this snapshot (the 29th of 289 at either d)."""
+    from oracle import oracle as O
+    opts, sim, g, o, window, cands = _snapshot_with_candidates(euroc_yaml, max_slam_features=20, max_slam_in_update=10,
+                                                               feat_rep_slam=rep)
+
+    def first_accepted(which, skip=()):
+        probe = O.OracleManager(opts)
+        sim.run([probe], n_frames=14)
+        for f, meas in cands:
+            short = _stereo_cut(meas, which)
+            if f in skip or len(short) != 2 * len(which):
+                continue
+            _sync(g, probe)
+            if probe.slam_delayed_init([(f, short)])[0]["used"]:
+                return f, short
+        return None
+
+    one_row = first_accepted([-1])
+    assert one_row is not None, "no two-measurement candidate passes the oracle"
+    five_rows = first_accepted([0, -1], skip=(one_row[0],))
+    assert five_rows is not None, "no two-stereo-time candidate passes the oracle"
+    full = next(c for c in cands if c[0] not in (one_row[0], five_rows[0]))
+    dset = [one_row, five_rows, full]
+    assert [len(m) for _, m in dset[:2]] == [2, 4] and len(full[1]) >= 12
+    assert len(set(m[1] for m in one_row[1])) == 1 and len(set(m[1] for m in five_rows[1])) == 2
+
+    _sync(g, o)
+    N0 = g.cov_dim()
+    rg, ro = g.slam_delayed_init(dset), o.slam_delayed_init(dset)
+    print("rep %d: used (device, oracle) %s" % (rep, [(a["used"], b["used"]) for a, b in zip(rg, ro)]))
+    assert ro[0]["used"], "the oracle rejected the one-row candidate it accepted alone"
+    assert _used(rg) == _used(ro)
+    used = sum(r["used"] for r in rg)
+    assert g.cov_dim() == N0 + d * used == o.get_cov().shape[0]
+    print("rel diff x %.2e P %.2e" % _same_state(g, o))
+    g.close()
+
+
 def test_slam_update_takes_its_list_as_one_batch(euroc_yaml):
     """UpdaterSLAM::update linearizes its whole list at one state and applies one EKF update; the chunks of
     max_slam_in_update are VioManager's.  With max_slam_in_update = 2 and 8 landmarks in one call, chunking

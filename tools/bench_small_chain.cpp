@@ -2,8 +2,7 @@
 // functions (libuvio_hp.so): launch_trsm_lt (X = V U^-T of the information form, N = 313, r = 148) and
 // launch_ekf_phaseA (k_ekf_MS: M = P[:, I] H^T and S_up = H T^T, N = 313, n = 163, r = 100, T given).
 // Prints the average µs per call over REPS back-to-back calls (HIP events, caches warm) and a checksum of the
-// outputs, so two library builds or an A/B switch (UVIO_HP_MS_SPLIT: M and S as two launches) can be compared
-// for speed and for bit-equality.  Results: profiles/r04t_small_chain.txt.
+// outputs, so two library builds can be compared for speed and for bit-equality.  Results: profiles/r04t_small_chain.txt.
 // Usage: bench_small_chain [REPS [N LDP n r LDH [TALL]]] (the k_ekf_MS / full-update shapes).
 // Build: hipcc -O2 -std=c++17 -I uvio_amd/csrc -I include tools/bench_small_chain.cpp -L uvio_amd -l:libuvio_hp.so
 //        -Wl,-rpath,'$ORIGIN/../uvio_amd' -o build/bench_small_chain

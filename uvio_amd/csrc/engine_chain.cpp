@@ -141,12 +141,8 @@ int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, s
     delayed.swap(keep);
   }
   if (up.empty() && slam_upd.empty() && delayed.empty()) return 0;
-  // the new landmarks' dimension d: 3, or 1 for the single inverse depth (whose delayed initialization exists only
-  // in the fused six-launch form)
+  // the new landmarks' dimension d: 3, or 1 for the single inverse depth
   const int rep_slam = o_.feat_rep_slam, d = landmark_rep_size(rep_slam);
-  if (!delayed.empty() && d == 1 && std::getenv("UVIO_HP_DI_UNFUSED"))
-    throw HpError(UVIO_HP_E_CONFIG, "UVIO_HP_DI_UNFUSED: the eight-launch delayed initialization has no d = 1 form "
-                                    "(feat_rep_slam: ANCHORED_INVERSE_DEPTH_SINGLE)");
   const int N0 = N_;
   const int K = (int)delayed.size();
   if (N0 + d * K > d_.ldp) throw HpError(UVIO_HP_E_CAPACITY, "covariance capacity exceeded");
@@ -583,34 +579,16 @@ int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, s
       EkfScratch sc = d_.ekf;
       sc.dx = region(new_region());
       double *Hrow = d_.H + (size_t)F.row_off * d_.ldh;
-      static const bool di_unfused = std::getenv("UVIO_HP_DI_UNFUSED") != nullptr;  // the eight-launch chain (A/B)
-      if (nup > 0 && !di_unfused) {
-        sc.chi2_gate = d_.acc;
-        // StateHelper::initialize's threshold: the rows it was given (after the bearing projection for d = 1)
-        sc.chi2_thr = o_.slam_chi2_multipler * chi2_table_[std::min(feat_rows_out(F), 999)];
-        sc.gate = nullptr;
-        KScope ks(&kprof_, KC_EKF);
-        launch_di_candidate(d_.stream, d_.P, d_.ldp, Ni, Hrow, d_.ldh, nup, n, cand->t_hidx, s2, sc, fo3 + j,
-                            sc.dx + Nn + 2, fr_cl, fr_cv, ncl, fr_cam, fr_camv, ncam, o_.do_calib_camera_pose,
-                            o_.do_calib_camera_intrinsics, sc.dx + Nn + 5, d);
-        kprof_.credit(KC_EKF, ekf_flops(Nn, n, nup), ekf_bytes(Nn, n, nup));
-        continue;
-      }
-      // (d = 3 from here: UVIO_HP_DI_UNFUSED with d = 1 was refused above, and nup >= 1 with two measurements)
-      launch_init_invertible(d_.stream, d_.P, d_.ldp, Ni, Hrow, d_.ldh, n, cand->t_hidx, nullptr, s2, sc, fo3 + j, d_.acc,
-                             sc.dx + Ni + 5);
-      if (nup > 0) {
-        sc.chi2_gate = d_.acc;
-        sc.chi2_thr = o_.slam_chi2_multipler * chi2_table_[std::min(2 * F.nmeas, 999)];
-        sc.gate = nullptr;
-        KScope ks(&kprof_, KC_EKF);
-        launch_ekf_update(d_.stream, d_.P, d_.ldp, Ni + 3, Hrow + 3 * (size_t)d_.ldh, d_.ldh, nup, n, cand->t_hidx,
-                          Hrow + 3 * (size_t)d_.ldh + n, d_.ldh, s2, sc);
-        kprof_.credit(KC_EKF, ekf_flops(Ni + 3, n, nup), ekf_bytes(Ni + 3, n, nup));
-      }
-      launch_chain_apply(d_.stream, fo3 + j, d_.acc, nup > 0 ? sc.neg : nullptr, nup > 0 ? sc.dx : nullptr, fr_cl, fr_cv,
-                         ncl, fr_cam, fr_camv, ncam, o_.do_calib_camera_pose, o_.do_calib_camera_intrinsics, nullptr, 0,
-                         d_.P, d_.ldp, Ni + 3, Ni, sc.dx + Ni + 8);
+      sc.chi2_gate = d_.acc;
+      // StateHelper::initialize's threshold: the rows it was given (after the bearing projection for d = 1)
+      sc.chi2_thr = o_.slam_chi2_multipler * chi2_table_[std::min(feat_rows_out(F), 999)];
+      sc.gate = nullptr;
+      KScope ks(&kprof_, KC_EKF);
+      // nup >= 1: a cleaned candidate has at least two measurements (launch_di_candidate refuses nup <= 0)
+      launch_di_candidate(d_.stream, d_.P, d_.ldp, Ni, Hrow, d_.ldh, nup, n, cand->t_hidx, s2, sc, fo3 + j,
+                          sc.dx + Nn + 2, fr_cl, fr_cv, ncl, fr_cam, fr_camv, ncam, o_.do_calib_camera_pose,
+                          o_.do_calib_camera_intrinsics, sc.dx + Nn + 5, d);
+      kprof_.credit(KC_EKF, ekf_flops(Nn, n, nup), ekf_bytes(Nn, n, nup));
     }
     ++p_epoch_;
   }

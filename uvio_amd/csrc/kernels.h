@@ -157,14 +157,14 @@ void launch_feature_linearize(hipStream_t s, const DBatchParams &bp, const DFeat
                               int *zero = nullptr);
 // batched chi2 gate (kernels_chi2.hip): T = H_all P[hidx, hidx], per-feature S / LDL^T / chi2;
 // rejected MSCKF / SLAM features get zero rows.  T_all: like H_all.
+// pcan: n^2 scratch for the gathered P_can of the tiled product (m >= 4096), or null
 // sbuf / sbuf_cap: the engine's buffer for the per-feature S of features too large for k_chi2's LDS staging
-// (formed by k_chi2_S over many CUs, grown here on demand); nullptr: k_chi2 forms S from global memory itself
+// (formed by k_chi2_S2 / k_chi2_S over many CUs, grown here on demand)
 // small_gate: every feature is mode 1 and acc_count is already zero (launch_feature_linearize's zero): with
 // max_rows_f <= 16 the gate is the single launch k_chi2_small
 void launch_chi2_batch(hipStream_t s, const DBatchParams &bp, const DFeat *feats, const double *P, const int *hidx,
                        double *H_all, int m, double *T_all, const double *chi2_table, DFeatOut *out, int max_rows_f,
-                       int *acc_count, double *pcan = nullptr,  // pcan: n^2 scratch for the gathered P_can
-                       double **sbuf = nullptr, size_t *sbuf_cap = nullptr, bool small_gate = false);
+                       int *acc_count, double *pcan, double **sbuf, size_t *sbuf_cap, bool small_gate);
 size_t feature_lds_bytes(int max_meas, int max_nf);
 
 // Compression: G = A^T A over rows of A = H_all (m x (n+1), ld = ldh), partials then Cholesky ->
@@ -223,7 +223,7 @@ struct EkfScratch {
   // rejected rows zeroed: k_ekf_MS then forms S_up = H T^T without recomputing T
   const double *Tall = nullptr;
   int ldt = 0;
-  double *M3 = nullptr;  // the delayed-init candidate's initialize_invertible M (N x 3)
+  double *M3 = nullptr;  // the delayed-init candidate's M3 = P[:, I] H_init^T (Ni x d, k_di_M), or null
   // optional, with Tall: the k-step mask of every 16-row tile of H (DBatchParams::kmask's second table)
   const unsigned long long *kmask_tile = nullptr;
 };
@@ -249,15 +249,6 @@ void launch_ekf_phaseA(hipStream_t s, const double *P, int ldp, int N, const dou
                        const int *hidx, double sigma2, EkfScratch &sc);
 void launch_ekf_phaseB(hipStream_t s, double *P, int ldp, int N, int r, const double *res, int res_stride,
                        EkfScratch &sc);
-// M = P[:, hidx] H^T (N x r, ld r) alone (k_ekf_MS without its S blocks); zero (optional): set to 0
-void launch_ekf_M(hipStream_t s, const double *P, int ldp, int N, const double *H, int ldh, int r, int n,
-                  const int *hidx, double *M, int *zero);
-// StateHelper::initialize_invertible for a 3-dof variable appended at N (StateHelper.cpp:484-577)
-// fout != nullptr: H_Linv = inverse of fout->HfR (formed on the device); gate: skipped when *gate == 0;
-// resout != nullptr: receives the residual column of rows 0..2 (Hx[a][n]), for the host's value update
-void launch_init_invertible(hipStream_t s, double *P, int ldp, int N, const double *Hx, int ldh, int n,
-                            const int *hidx, const double *HLinv, double s2, EkfScratch &sc,
-                            const DFeatOut *fout = nullptr, const int *gate = nullptr, double *resout = nullptr);
 // the JPL pose value behind a clone / camera-extrinsic table entry (PoseJPL: q_GtoI / q_ItoC, position) and its
 // covariance id, updated on the device inside a delayed-initialization chain
 struct DPoseVal {
@@ -277,7 +268,9 @@ void launch_chain_apply(hipStream_t s, const DFeatOut *fout, const int *gate, co
 // One delayed-initialization candidate (StateHelper::initialize): initialize_invertible of the landmark into the
 // slot Ni (H_Linv from fout->HfR, rows Hrow[0..d-1]), the chi2-gated EKF update of the other nup rows (Hrow + d,
 // residual in column n; sc.chi2_gate: in = the linearization gate, out = accepted; sc.chi2_thr), and the chain
-// step of launch_chain_apply (tables moved by dx, or the slot cleared; [accepted, neg] into out), as six launches.
+// step of launch_chain_apply (tables moved by dx, or the slot cleared; [accepted, neg] into out), as six launches
+// with the linearization before it (k_feature; here k_di_M, k_di_S, k_ekf_fact, k_ekf_WP, k_chain_apply).
+// 1 <= nup < 256: a candidate has at least two measurements, and anything else throws.
 // resout receives the residual column of the d initializing rows.  d: the landmark dimension, 3 or 1 (the single
 // inverse depth: H_Linv = 1 / HfR[0]); a template parameter of the kernels, so d = 3 runs the code it always ran.
 void launch_di_candidate(hipStream_t s, double *P, int ldp, int Ni, const double *Hrow, int ldh, int nup, int n,

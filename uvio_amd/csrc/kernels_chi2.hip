@@ -622,11 +622,10 @@ void launch_chi2_batch(hipStream_t s, const DBatchParams &bp, const DFeat *feats
   if (granted < 0) granted = set_dyn_lds((const void *)chi2_fn, kMaxDynLds);
   if (bytes > 64 * 1024 && (int)bytes > granted)
     throw std::runtime_error("k_chi2 needs " + std::to_string(bytes) + " B of LDS, granted " + std::to_string(granted));
-  // features too large for the LDS staging: S over many CUs first (k_chi2_S), k_chi2 reads it
+  // features too large for the LDS staging: S over many CUs first (k_chi2_S2 / k_chi2_S), k_chi2 reads it
   double *Sg = nullptr;
   size_t stride = 0;
-  static const bool no_s = std::getenv("UVIO_HP_NO_CHI2_S") != nullptr;  // A/B switch: k_chi2 forms S itself
-  if (!use_lds && sbuf && sbuf_cap && !no_s) {
+  if (!use_lds) {
     stride = (size_t)max_rows_f * (max_rows_f | 1);
     const size_t need = stride * (size_t)bp.nfeat;
     if (need > *sbuf_cap) {
@@ -644,9 +643,8 @@ void launch_chi2_batch(hipStream_t s, const DBatchParams &bp, const DFeat *feats
     }
     Sg = *sbuf;
     const int nt = (max_rows_f + 15) / 16, groups = (nt * (nt + 1) / 2 + kChiSWaves - 1) / kChiSWaves;
-    static const bool per_tile = std::getenv("UVIO_HP_CHI2_S_TILES") != nullptr;  // A/B switch: k_chi2_S
     const size_t s2_bytes = (size_t)2 * 16 * nt * (kS2KC + 1) * sizeof(double);
-    if (!per_tile && nt * (nt + 1) / 2 <= kS2Waves * kS2Tiles) {
+    if (nt * (nt + 1) / 2 <= kS2Waves * kS2Tiles) {
       static int granted2 = -1;
       if (granted2 < 0) granted2 = set_dyn_lds((const void *)k_chi2_S2, kMaxDynLds);
       if (s2_bytes > 64 * 1024 && (int)s2_bytes > granted2)

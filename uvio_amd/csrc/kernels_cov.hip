@@ -749,7 +749,7 @@ static void launch_gemm_mfma(hipStream_t s, int ta, int tb, int tri, int symA, i
 
 // Single-workgroup Cholesky factors of the information-form update (dense_lds.h ldl_wave: one wave
 // factors each 16-column panel, the other waves do the rank-16 updates).  Storage mode: 0 = square in
-// LDS, 1 = packed lower triangle in LDS (n up to ~195), 2 = square in the global scratch gbuf.
+// LDS, 1 = packed lower triangle in LDS (n up to 195); a larger factor goes through the split below.
 // L_c = L_u D^1/2; an extra right-hand-side row b leaves as L_c^-1 b = D^1/2 (D^-1 L_u^-1 b).
 // Dinv: the inverses of L_c's 16 x 16 diagonal blocks for k_trsm_lt (k_trinv16's layout: block b row-major at
 // Dinv + 256 b, rows past n identity), D^-1/2 times the unit-lower block inverses the factorization forms
@@ -771,11 +771,10 @@ __device__ __forceinline__ void info_chol_body(double *A, LA la, double *Dd, int
 template <int W, int MODE>
 __global__ void __launch_bounds__(kFactThreads) k_info_cholP(const double *__restrict__ P, int ldp, const int *__restrict__ hidx,
                                                     int n, double *__restrict__ Laug, double *__restrict__ Lout,
-                                                    double *gbuf, int mode, double *__restrict__ Dinv) {
+                                                    double *__restrict__ Dinv) {
   constexpr int PACKED = MODE == 1;
   extern __shared__ double lds[];
-  double *A = (MODE == 2) ? gbuf : lds;
-  (void)mode;
+  double *A = lds;
   const int ld = n | 1;
   const size_t asz = PACKED ? packed_lds_doubles(n) : (size_t)n * ld;
   double *Dd = A + asz;
@@ -810,12 +809,11 @@ __global__ void __launch_bounds__(kFactThreads) k_info_cholP(const double *__res
 // Writes U (n x n, ld n) and w (n).
 template <int W, int MODE>
 __global__ void __launch_bounds__(kFactThreads) k_info_cholZ(const double *__restrict__ E, int n, double s2,
-                                                    double *__restrict__ Uout, double *__restrict__ w, double *gbuf,
-                                                    int mode, double *__restrict__ Dinv) {
+                                                    double *__restrict__ Uout, double *__restrict__ w,
+                                                    double *__restrict__ Dinv) {
   constexpr int PACKED = MODE == 1;
   extern __shared__ double lds[];
-  double *A = (MODE == 2) ? gbuf : lds;
-  (void)mode;
+  double *A = lds;
   const int ld = n | 1;
   const int na = n + 1;
   const size_t asz = PACKED ? packed_lds_doubles(na) : (size_t)na * ld;
@@ -844,23 +842,20 @@ __global__ void __launch_bounds__(kFactThreads) k_info_cholZ(const double *__res
 }
 // the instantiation for a factor of `rows` rows (panel rows per lane) and storage mode
 template <class KP>
-static KP pick_info_kernel(const KP (&tab)[5][3], int rows, int mode) {
+static KP pick_info_kernel(const KP (&tab)[5][2], int rows, int mode) {
   return tab[panel_waves(rows) - 1][mode];
 }
-typedef void (*CholPFn)(const double *, int, const int *, int, double *, double *, double *, int, double *);
-typedef void (*CholZFn)(const double *, int, double, double *, double *, double *, int, double *);
-static const CholPFn kCholP[5][3] = {{k_info_cholP<1, 0>, k_info_cholP<1, 1>, k_info_cholP<1, 2>},
-                                     {k_info_cholP<2, 0>, k_info_cholP<2, 1>, k_info_cholP<2, 2>},
-                                     {k_info_cholP<3, 0>, k_info_cholP<3, 1>, k_info_cholP<3, 2>},
-                                     {k_info_cholP<4, 0>, k_info_cholP<4, 1>, k_info_cholP<4, 2>},
-                                     {k_info_cholP<5, 0>, k_info_cholP<5, 1>, k_info_cholP<5, 2>}};
-static const CholZFn kCholZ[5][3] = {{k_info_cholZ<1, 0>, k_info_cholZ<1, 1>, k_info_cholZ<1, 2>},
-                                     {k_info_cholZ<2, 0>, k_info_cholZ<2, 1>, k_info_cholZ<2, 2>},
-                                     {k_info_cholZ<3, 0>, k_info_cholZ<3, 1>, k_info_cholZ<3, 2>},
-                                     {k_info_cholZ<4, 0>, k_info_cholZ<4, 1>, k_info_cholZ<4, 2>},
-                                     {k_info_cholZ<5, 0>, k_info_cholZ<5, 1>, k_info_cholZ<5, 2>}};
+typedef void (*CholPFn)(const double *, int, const int *, int, double *, double *, double *);
+typedef void (*CholZFn)(const double *, int, double, double *, double *, double *);
+static const CholPFn kCholP[5][2] = {{k_info_cholP<1, 0>, k_info_cholP<1, 1>}, {k_info_cholP<2, 0>, k_info_cholP<2, 1>},
+                                     {k_info_cholP<3, 0>, k_info_cholP<3, 1>}, {k_info_cholP<4, 0>, k_info_cholP<4, 1>},
+                                     {k_info_cholP<5, 0>, k_info_cholP<5, 1>}};
+static const CholZFn kCholZ[5][2] = {{k_info_cholZ<1, 0>, k_info_cholZ<1, 1>}, {k_info_cholZ<2, 0>, k_info_cholZ<2, 1>},
+                                     {k_info_cholZ<3, 0>, k_info_cholZ<3, 1>}, {k_info_cholZ<4, 0>, k_info_cholZ<4, 1>},
+                                     {k_info_cholZ<5, 0>, k_info_cholZ<5, 1>}};
 
-// storage mode and dynamic LDS bytes of an info-form factor of nrows x n (+ the n doubles of D)
+// storage mode and dynamic LDS bytes of an info-form factor of nrows x n (+ the n doubles of D); 2: neither
+// layout fits in LDS, the factor runs through the split (launch_info_split)
 static int info_chol_mode(int nrows, int n, size_t *bytes) {
   const size_t sq = ((size_t)nrows * (n | 1) + n) * sizeof(double);
   const size_t pk = (packed_lds_doubles(nrows) + n) * sizeof(double);
@@ -878,7 +873,7 @@ static int info_chol_mode(int nrows, int n, size_t *bytes) {
 
 
 // ---- the information-form factors too large for LDS (n + 1 rows beyond the packed triangle, cfg5: 243): split ----
-// Mode 2 ran the one-workgroup factor out of global memory (cfg5: P_II 350 us, Z 290 us per launch).  The split runs
+// The one-workgroup factor once ran these out of global memory (cfg5: P_II 350 us, Z 290 us a launch).  The split runs
 // the same right-looking LDL^T in four launches, every stored value the one the one-workgroup factor computes:
 //   1  the first n1 columns (a multiple of 16) over ALL rows in LDS, the rows below n1 held in a trapezoid layout
 //      (ldl_wave_inv treats them as right-hand-side rows: the same panel steps and rank-16 tiles as in the full
@@ -1039,14 +1034,15 @@ static const Split1Fn kSplit1[2][5] = {
 static const Split3Fn kSplit3[5] = {k_info_split3<1>, k_info_split3<2>, k_info_split3<3>, k_info_split3<4>,
                                     k_info_split3<5>};
 // the split's first block: the widest multiple of 16 whose trapezoid fits in LDS and leaves a trailing block that
-// fits packed; 0 when there is none
+// fits packed.  There is one for every factor that needs the split (storage mode 2: 196 rows or more) up to
+// kWaveMaxRows rows: n1 runs from 176 at 196 rows down to 80 at 256.
 static int info_split_n1(int N, int n) {
   for (int n1 = (n - 1) / 16 * 16; n1 >= 16; n1 -= 16) {
     const size_t t1 = trap_lds_doubles(N, n1) * sizeof(double);
     const size_t t3 = (packed_lds_doubles(N - n1) + (n - n1)) * sizeof(double);
     if (t1 <= (size_t)kMaxDynLds && t3 <= (size_t)kMaxDynLds) return n1;
   }
-  return 0;
+  throw std::runtime_error("information-form factor with no split that fits in LDS");
 }
 // the factor of an N x n matrix (N = n or n + 1) from SRC through the split; G (ld ldg) and Dg scratch
 template <int SRC, int OUT>
@@ -1162,8 +1158,8 @@ __global__ void __launch_bounds__(256) k_info_P(double *__restrict__ P, int ldp,
 // The chain splits at the Gram: the prefactor (P_II = L L^T and V = P[:,I] L^-T) reads only P and the
 // column map, both fixed once the batch's columns are known, so the engine runs it on a side stream while
 // the feature group forms the rows (launch_ekf_info_pre); launch_ekf_info_post is the rest.
-// Scratch: sc.S holds Laug | L_P | T1 | E | U (5 (n+1)^2), sc.M holds V (and is cholP's global work buffer
-// before that), sc.W is cholZ's global work buffer and then X, sc.Dinv the diagonal-block inverses.
+// Scratch: sc.S holds Laug | L_P | T1 | E | U (5 (n+1)^2), sc.M holds V (and the split P_II factor's work
+// buffer before that), sc.W is the split Z factor's work buffer and then X, sc.Dinv the diagonal-block inverses.
 void launch_ekf_info_pre(hipStream_t s, const double *P, int ldp, int N, int n, const int *hidx, EkfScratch &sc) {
   const int na = n + 1;
   double *Laug = sc.S;
@@ -1172,13 +1168,12 @@ void launch_ekf_info_pre(hipStream_t s, const double *P, int ldp, int N, int n, 
   if (n + 1 > kWaveMaxRows) throw std::runtime_error("information-form update wider than the factorization panel");
   size_t b1 = 0;
   const int m1 = info_chol_mode(n, n, &b1);
-  static const bool no_split = std::getenv("UVIO_HP_NO_INFO_SPLIT") != nullptr;  // A/B: the global-memory factor
-  const int s1 = (m1 == 2 && !no_split) ? info_split_n1(n, n) : 0;
-  if (s1 > 0)  // the raw pivots in T1 (free until the post half)
-    launch_info_split<0, 0>(s, s1, P, ldp, hidx, 0.0, n, n, sc.M, n | 1, Lf + (size_t)n * n, sc.Dinv, Laug, Lf);
+  if (m1 == 2)  // the raw pivots in T1 (free until the post half)
+    launch_info_split<0, 0>(s, info_split_n1(n, n), P, ldp, hidx, 0.0, n, n, sc.M, n | 1, Lf + (size_t)n * n, sc.Dinv,
+                            Laug, Lf);
   else
     hipLaunchKernelGGL(pick_info_kernel(kCholP, n, m1), dim3(1), dim3(kFactThreads), b1, s, P, ldp, hidx, n, Laug, Lf,
-                       sc.M, m1, sc.Dinv);
+                       sc.Dinv);
   launch_trsm_lt(s, P, ldp, hidx, N, n, Lf, n, sc.Dinv, sc.M, false);  // V = P[:,I] L^-T
 }
 
@@ -1196,13 +1191,12 @@ void launch_ekf_info_post(hipStream_t s, double *P, int ldp, int N, const double
   launch_gemm_mfma(s, 1, 0, 2, 0, na, na, na, Laug, na, T1, na, E, na);     // Laug^T (G Laug)
   size_t b2 = 0;
   const int m2 = info_chol_mode(n + 1, n, &b2);
-  static const bool no_split = std::getenv("UVIO_HP_NO_INFO_SPLIT") != nullptr;
-  const int s2 = (m2 == 2 && !no_split) ? info_split_n1(n + 1, n) : 0;
-  if (s2 > 0)  // the raw pivots in T1 (consumed by the second product above)
-    launch_info_split<1, 1>(s, s2, E, na, nullptr, sigma2, n + 1, n, sc.W, n | 1, T1, sc.Dinv, Uf, w);
+  if (m2 == 2)  // the raw pivots in T1 (consumed by the second product above)
+    launch_info_split<1, 1>(s, info_split_n1(n + 1, n), E, na, nullptr, sigma2, n + 1, n, sc.W, n | 1, T1, sc.Dinv, Uf,
+                            w);
   else
-    hipLaunchKernelGGL(pick_info_kernel(kCholZ, n + 1, m2), dim3(1), dim3(kFactThreads), b2, s, E, n, sigma2, Uf, w, sc.W,
-                       m2, sc.Dinv);
+    hipLaunchKernelGGL(pick_info_kernel(kCholZ, n + 1, m2), dim3(1), dim3(kFactThreads), b2, s, E, n, sigma2, Uf, w,
+                       sc.Dinv);
   launch_trsm_lt(s, sc.M, n, nullptr, N, n, Uf, n, sc.Dinv, sc.W, false);  // X = V U^-T
   const int nb = (N + 15) / 16;
   const int per = (nb * (nb + 1) / 2 + kInfoPXcds - 1) / kInfoPXcds;
@@ -1214,81 +1208,6 @@ void launch_ekf_info(hipStream_t s, double *P, int ldp, int N, const double *par
                      const int *hidx, double sigma2, double *Gbuf, EkfScratch &sc) {
   launch_ekf_info_pre(s, P, ldp, N, n, hidx, sc);
   launch_ekf_info_post(s, P, ldp, N, partials, nch, n, sigma2, Gbuf, sc);
-}
-
-// StateHelper::initialize_invertible (StateHelper.cpp:484-577) for a 3-dof landmark appended at N:
-// M = P[:, hidx] Hx^T is in sc.M (N x 3, from launch_ekf_M); Hx (3 x n, ld), HLinv (3x3, device), s2.
-// With fout (delayed init enqueued behind its feature group): H_Linv is the inverse of the feature's
-// H_finit (DFeatOut::HfR), formed here with the host's cofactor formula, and the whole step is skipped
-// when the gate (the batch's accepted-feature count) is 0.
-__global__ void k_init_invertible(double *__restrict__ P, int ldp, int N, const double *__restrict__ M,
-                                  const double *__restrict__ Hx, int ldh, int n, const int *__restrict__ hidx,
-                                  const double *__restrict__ HLinv_in, double s2, const DFeatOut *__restrict__ fout,
-                                  const int *__restrict__ gate, double *__restrict__ resout) {
-  __shared__ double S3[9], PLL[9], Hinv[9];
-  if (resout && blockIdx.x == 0 && threadIdx.x < 3) resout[threadIdx.x] = Hx[(size_t)threadIdx.x * ldh + n];
-  if (gate && *gate == 0) return;
-  if (threadIdx.x == 0) {
-    if (fout)
-      inv3_cofactor(fout->HfR, Hinv);
-    else
-      for (int k = 0; k < 9; k++) Hinv[k] = HLinv_in[k];
-  }
-  __syncthreads();
-  const double *HLinv = Hinv;
-  int t = threadIdx.x + blockIdx.x * blockDim.x;
-  if (blockIdx.x == 0) {
-    // S3 = Hx M[hidx, :] + s2 I: each of the 9 entries summed by 28 threads over strided k, the 28
-    // partials then added in fixed order (blockDim = 256 >= 9 x 28)
-    __shared__ double part[9][28];
-    const int e = threadIdx.x / 28, j = threadIdx.x % 28;
-    if (e < 9) {
-      const int a = e / 3, b = e % 3;
-      double acc = 0.0;
-      for (int k = j; k < n; k += 28) acc += Hx[(size_t)a * ldh + k] * M[(size_t)hidx[k] * 3 + b];
-      part[e][j] = acc;
-    }
-    __syncthreads();
-    if (threadIdx.x < 9) {
-      const int a = threadIdx.x / 3, b = threadIdx.x % 3;
-      double acc = 0.0;
-      for (int q = 0; q < 28; q++) acc += part[threadIdx.x][q];
-      // M.selfadjointView<Upper>(): use the upper element for both halves
-      S3[threadIdx.x] = acc + (a == b ? s2 : 0.0);
-    }
-  }
-  __syncthreads();
-  if (blockIdx.x == 0 && threadIdx.x < 9) {
-    int a = threadIdx.x / 3, b = threadIdx.x % 3;
-    double acc = 0.0;
-    for (int c = 0; c < 3; c++)
-      for (int e = 0; e < 3; e++) {
-        double sce = (c <= e) ? S3[c * 3 + e] : S3[e * 3 + c];
-        acc += HLinv[a * 3 + c] * sce * HLinv[b * 3 + e];
-      }
-    PLL[threadIdx.x] = acc;
-  }
-  __syncthreads();
-  if (t < N * 3) {
-    int i = t / 3, a = t % 3;
-    double acc = 0.0;
-    for (int b = 0; b < 3; b++) acc += M[(size_t)i * 3 + b] * HLinv[a * 3 + b];
-    P[(size_t)i * ldp + N + a] = -acc;
-    P[(size_t)(N + a) * ldp + i] = -acc;
-  }
-  if (blockIdx.x == 0 && threadIdx.x < 9) {
-    int a = threadIdx.x / 3, b = threadIdx.x % 3;
-    P[(size_t)(N + a) * ldp + N + b] = PLL[threadIdx.x];
-  }
-}
-
-void launch_init_invertible(hipStream_t s, double *P, int ldp, int N, const double *Hx, int ldh, int n,
-                            const int *hidx, const double *HLinv, double s2, EkfScratch &sc, const DFeatOut *fout,
-                            const int *gate, double *resout) {
-  launch_ekf_M(s, P, ldp, N, Hx, ldh, 3, n, hidx, sc.M, nullptr);
-  int nt = N * 3;
-  hipLaunchKernelGGL(k_init_invertible, dim3((nt + 255) / 256), dim3(256), 0, s, P, ldp, N, sc.M, Hx, ldh, n, hidx,
-                     HLinv, s2, fout, gate, resout);
 }
 
 static void ensure_lds_attrs() {

@@ -2,8 +2,9 @@
 // launches whose products all run on the FP64 matrix cores (v_mfma_f64_16x16x4f64):
 //
 //   k_ekf_MS   grid:  M = P[:, I] H^T (N x r; one 16-row block per workgroup, the P rows gathered once
-//                     into LDS) and, in the same launch, S_up = H P_II H^T + s2 I (one 16-column block of S
-//                     per workgroup: T = P_II H_b^T into LDS, then the upper tiles H_a T)
+//                     into LDS) and S_up = H P_II H^T + s2 I = H T^T (one upper 16x16 tile pair per wave), with
+//                     T = H P_II read from the batch's chi2 gate in the same launch, or gathered from the rows
+//                     I of this update's own M in a second launch
 //   k_ekf_fact one workgroup: LDL^T of [S ; r^T] in LDS with the unit-lower inverse alongside (dense_lds.h
 //                     ldl_wave) -> L^-1, y = L^-1 r, and StateHelper::initialize's chi2 gate on y
 //   k_ekf_WP   grid over the upper 16x16 tile pairs (bi <= bj) of P: W_b = M_b L^-T for both row blocks
@@ -17,7 +18,6 @@
 //
 // MFMA operand layout (f64 16x16x4): A (16x4) lane l holds A[l & 15][l >> 4]; B (4x16) lane l holds
 // B[l >> 4][l & 15]; C/D register q of lane l is D[(l >> 4) + 4 q][l & 15].
-#include <cstdlib>
 #include <algorithm>
 #include <stdexcept>
 
@@ -27,7 +27,8 @@
 namespace uvhp {
 
 // ---------------------------------------------------------------------------------------------------
-// K1: M (blocks 0 .. nbM-1) and S_up (blocks nbM .. nbM + ceil(r/16) - 1; none when Sup is null)
+// K1, two parts: M (blocks 0 .. nbM-1) and the upper tile pairs of S_up (blocks nbM ..; 8 pairs each).  Tall is
+// non-null whenever a block index reaches nbM or beyond: a launch without it has exactly nbM blocks.
 // km (optional, with Tall: a SLAM chunk): the k-step mask of every 16-row tile of H (kernels.h DBatchParams::kmask).
 // Column tile t of M and the S tile pairs (a, b) have H's row tile t / a as an operand, so their chains visit only
 // its set steps (dense_lds.h tile_chain_masked: the same values).
@@ -77,117 +78,47 @@ __global__ void __launch_bounds__(kMSThreads) k_ekf_MS(const double *__restrict_
     }
     return;
   }
-  if (Tall) {
-    // T = H P_II is already in HBM from the batch's chi2 gate (k_gemm_HPg, rejected features' rows zeroed
-    // there with their H rows), so S_up[a][b] = H_a T_b^T directly: one upper tile pair (a <= b) per wave,
-    // one chain of loads instead of forming T_b first (same products, same ascending k order).
-    // ldt < 0: Tall is this update's M = P[:, I] H^T (N x r, launched after the M blocks), whose rows hidx are
-    // T^T: T[b][k] = M[hidx[k]][b], the products and k order with which the column blocks below form T.
-    const bool gath = ldt < 0;
-    int *hs = (int *)sh;
-    if (gath) {
-      for (int k = threadIdx.x; k < n; k += blockDim.x) hs[k] = hidx[k];
-      __syncthreads();
-    }
-    const int nt = (r + 15) / 16;
-    int pair = (blockIdx.x - nbM) * (kMSThreads / 64) + wid, at = 0;
-    if (pair >= nt * (nt + 1) / 2) return;
-    while (pair >= nt - at) {
-      pair -= nt - at;
-      at++;
-    }
-    const int bt = at + pair;
-    const int ar = 16 * at + r16, br = 16 * bt + r16;
-    const double *Ha = H + (size_t)min(ar, r - 1) * ldh;
-    const double *Tb = gath ? Tall + min(br, r - 1) : Tall + (size_t)min(br, r - 1) * ldt;
-    const bool av = ar < r, bv = br < r;
-    dbl4 acc = {0.0, 0.0, 0.0, 0.0};
-    auto la = [&](int k) { return av ? Ha[k] : 0.0; };
-    auto lb = [&](int k) { return bv ? (gath ? Tb[(size_t)hs[k] * r] : Tb[k]) : 0.0; };
-    if (km)
-      acc = tile_chain_masked<16>(kmask_uniform(km[2 * at]), kmask_uniform(km[2 * at + 1]), n, kq, la, lb, acc);
-    else
-      acc = tile_chain<16>(0, n, kq, la, lb, acc);
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      const int row = 16 * at + kq + 4 * q, col = 16 * bt + r16;
-      if (row < r && col < r) Sup[(size_t)row * r + col] = acc[q] + (row == col ? s2 : 0.0);
-    }
-    return;
+  // T = H P_II is already in HBM from the batch's chi2 gate (k_gemm_HPg, rejected features' rows zeroed
+  // there with their H rows), so S_up[a][b] = H_a T_b^T directly: one upper tile pair (a <= b) per wave,
+  // one chain of loads instead of forming T_b first (same products, same ascending k order).
+  // ldt < 0: Tall is this update's M = P[:, I] H^T (N x r, launched after the M blocks), whose rows hidx are
+  // T^T: T[b][k] = M[hidx[k]][b].
+  const bool gath = ldt < 0;
+  int *hs = (int *)sh;
+  if (gath) {
+    for (int k = threadIdx.x; k < n; k += blockDim.x) hs[k] = hidx[k];
+    __syncthreads();
   }
-  // S column block b: T = P_II H_b^T (n x 16) into LDS, then S_up[a-tile][b] = H_a T for a <= b
-  const int jb = blockIdx.x - nbM, j0 = 16 * jb;
-  const int npad = (n + 15) / 16 * 16;
-  double *Ts = sh;                                  // npad x 17
-  int *hs = (int *)(sh + (size_t)npad * 17);        // hidx
-  for (int k = threadIdx.x; k < n; k += blockDim.x) hs[k] = hidx[k];
-  __syncthreads();
-  {
-    const int jr = j0 + r16;
-    const double *Hb = H + (size_t)min(jr, r - 1) * ldh;
-    const bool jv = jr < r;
-    for (int kt = wid; kt < npad / 16; kt += kMSThreads / 64) {
-      const int row = 16 * kt + r16;
-      const double *Prow = P + (size_t)hs[min(row, n - 1)] * ldp;
-      const bool rv = row < n;
-      dbl4 acc = {0.0, 0.0, 0.0, 0.0};
-      acc = tile_chain<16>(
-          0, n, kq, [&](int l) { return rv ? Prow[hs[l]] : 0.0; }, [&](int l) { return jv ? Hb[l] : 0.0; }, acc);
-#pragma unroll
-      for (int q = 0; q < 4; q++) Ts[(16 * kt + kq + 4 * q) * 17 + r16] = acc[q];
-    }
+  const int nt = (r + 15) / 16;
+  int pair = (blockIdx.x - nbM) * (kMSThreads / 64) + wid, at = 0;
+  if (pair >= nt * (nt + 1) / 2) return;
+  while (pair >= nt - at) {
+    pair -= nt - at;
+    at++;
   }
-  __syncthreads();
-  for (int at = wid; at <= jb; at += kMSThreads / 64) {
-    const int ar = 16 * at + r16;
-    const double *Ha = H + (size_t)min(ar, r - 1) * ldh;
-    const bool av = ar < r;
-    dbl4 acc = {0.0, 0.0, 0.0, 0.0};
-    acc = tile_chain<16>(
-        0, n, kq, [&](int k) { return av ? Ha[k] : 0.0; }, [&](int k) { return Ts[k * 17 + r16]; }, acc);
+  const int bt = at + pair;
+  const int ar = 16 * at + r16, br = 16 * bt + r16;
+  const double *Ha = H + (size_t)min(ar, r - 1) * ldh;
+  const double *Tb = gath ? Tall + min(br, r - 1) : Tall + (size_t)min(br, r - 1) * ldt;
+  const bool av = ar < r, bv = br < r;
+  dbl4 acc = {0.0, 0.0, 0.0, 0.0};
+  auto la = [&](int k) { return av ? Ha[k] : 0.0; };
+  auto lb = [&](int k) { return bv ? (gath ? Tb[(size_t)hs[k] * r] : Tb[k]) : 0.0; };
+  if (km)
+    acc = tile_chain_masked<16>(kmask_uniform(km[2 * at]), kmask_uniform(km[2 * at + 1]), n, kq, la, lb, acc);
+  else
+    acc = tile_chain<16>(0, n, kq, la, lb, acc);
 #pragma unroll
-    for (int q = 0; q < 4; q++) {
-      const int row = 16 * at + kq + 4 * q, col = j0 + r16;
-      if (row < r && col < r) Sup[(size_t)row * r + col] = acc[q] + (row == col ? s2 : 0.0);
-    }
+  for (int q = 0; q < 4; q++) {
+    const int row = 16 * at + kq + 4 * q, col = 16 * bt + r16;
+    if (row < r && col < r) Sup[(size_t)row * r + col] = acc[q] + (row == col ? s2 : 0.0);
   }
 }
 
-// M = P[:, I] H^T for r <= 4 rows (initialize_invertible's 3 x n block): a GEMV per covariance row, one
-// wavefront per row with the lanes over the columns and a butterfly reduction (the 16-row MFMA blocks of
-// k_ekf_MS would waste 13 of 16 output columns and serialize their loads per tile)
+// initialize_invertible's M has at most this many columns (k_di_M's GEMV accumulators)
 constexpr int kSmallMRows = 4;
-__global__ void __launch_bounds__(256) k_ekf_M_small(const double *__restrict__ P, int ldp, int N,
-                                                     const double *__restrict__ H, int ldh, int r, int n,
-                                                     const int *__restrict__ hidx, double *__restrict__ M, int *zero) {
-  if (zero && blockIdx.x == 0 && threadIdx.x == 0) *zero = 0;
-  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= N) return;
-  const double *Pr = P + (size_t)row * ldp;
-  double acc[kSmallMRows] = {0.0, 0.0, 0.0, 0.0};
-  for (int k = lane; k < n; k += 64) {
-    const double p = Pr[hidx[k]];
-#pragma unroll
-    for (int b = 0; b < kSmallMRows; b++)
-      if (b < r) acc[b] = fma(p, H[(size_t)b * ldh + k], acc[b]);
-  }
-#pragma unroll
-  for (int b = 0; b < kSmallMRows; b++)
-    for (int o = 32; o > 0; o >>= 1) acc[b] += __shfl_xor(acc[b], o, 64);
-  if (lane < r) {
-    double v = acc[0];
-#pragma unroll
-    for (int b = 1; b < kSmallMRows; b++)
-      if (lane == b) v = acc[b];
-    M[(size_t)row * r + lane] = v;
-  }
-}
-
-static size_t ekf_ms_lds_bytes(int n, bool with_S) {
-  size_t bm = (size_t)16 * (n | 1) * sizeof(double);
-  size_t bs = with_S ? (size_t)(n + 15) / 16 * 16 * 17 * sizeof(double) + (size_t)n * sizeof(int) : 0;
-  return bm > bs ? bm : bs;
-}
+// the M blocks' 16 x (n | 1) doubles; the gathered S blocks' n ints fit inside them
+static size_t ekf_ms_lds_bytes(int n) { return (size_t)16 * (n | 1) * sizeof(double); }
 
 // ---------------------------------------------------------------------------------------------------
 // K2: one workgroup.  [S ; r^T] (S from the upper triangle of S_up = selfadjointView<Upper>,
@@ -499,52 +430,25 @@ static void ensure_ekf_lds_attrs() {
   done = true;
 }
 
-void launch_ekf_M(hipStream_t s, const double *P, int ldp, int N, const double *H, int ldh, int r, int n,
-                  const int *hidx, double *M, int *zero) {
-  if (r <= kSmallMRows) {
-    hipLaunchKernelGGL(k_ekf_M_small, dim3((N + 3) / 4), dim3(256), 0, s, P, ldp, N, H, ldh, r, n, hidx, M, zero);
-    return;
-  }
-  ensure_ekf_lds_attrs();
-  const size_t lds = ekf_ms_lds_bytes(n, false);
-  if (lds > (size_t)kMaxDynLds) throw std::runtime_error("EKF update with too many columns for k_ekf_MS");
-  const int nbM = (N + 15) / 16;
-  hipLaunchKernelGGL(k_ekf_MS, dim3(nbM), dim3(kMSThreads), lds, s, P, ldp, N, H, ldh, r, n, hidx, 0.0, M,
-                     (double *)nullptr, nbM, zero, (const double *)nullptr, 0, (const unsigned long long *)nullptr);
-}
-
 void launch_ekf_phaseA(hipStream_t s, const double *P, int ldp, int N, const double *H, int ldh, int r, int n,
                        const int *hidx, double sigma2, EkfScratch &sc) {
   ensure_ekf_lds_attrs();
-  const size_t lds = ekf_ms_lds_bytes(n, true);
+  const size_t lds = ekf_ms_lds_bytes(n);
   if (lds > (size_t)kMaxDynLds) throw std::runtime_error("EKF update with too many columns for k_ekf_MS");
   const int nbM = (N + 15) / 16, nt = (r + 15) / 16;
   const int wpb = kMSThreads / 64;
-  const double *Tall = sc.Tall;
-  const int nbS = Tall ? (nt * (nt + 1) / 2 + wpb - 1) / wpb : nt;  // tile pairs, a wave each / column blocks
+  const int nbS = (nt * (nt + 1) / 2 + wpb - 1) / wpb;  // the upper tile pairs, a wave each
   double *Sup = sc.S + 2 * (size_t)r * r;
-  // No T from a chi2 gate (the delayed initialization's update): S from this update's own M in a second
-  // launch (rows hidx of M are T^T) instead of each S column block forming T from P (r04v: 26 us per launch in
-  // the cfg3 frame).  UVIO_HP_MS_FROM_P=1: the one-launch form (A/B).
-  static const bool from_p = std::getenv("UVIO_HP_MS_FROM_P") != nullptr;
-  if (!Tall && !from_p) {
-    const int nbG = (nt * (nt + 1) / 2 + wpb - 1) / wpb;
+  if (!sc.Tall) {
+    // No T from a chi2 gate: S from this update's own M in a second launch (rows hidx of M are T^T)
     hipLaunchKernelGGL(k_ekf_MS, dim3(nbM), dim3(kMSThreads), lds, s, P, ldp, N, H, ldh, r, n, hidx, sigma2, sc.M, Sup,
                        nbM, sc.neg, (const double *)nullptr, 0, (const unsigned long long *)nullptr);
-    hipLaunchKernelGGL(k_ekf_MS, dim3(nbG), dim3(kMSThreads), lds, s, P, ldp, N, H, ldh, r, n, hidx, sigma2, sc.M, Sup,
+    hipLaunchKernelGGL(k_ekf_MS, dim3(nbS), dim3(kMSThreads), lds, s, P, ldp, N, H, ldh, r, n, hidx, sigma2, sc.M, Sup,
                        0, (int *)nullptr, (const double *)sc.M, -1, (const unsigned long long *)nullptr);
     return;
   }
-  static const bool split = std::getenv("UVIO_HP_MS_SPLIT") != nullptr;  // diagnostic: M, then S, as two launches
-  if (split) {
-    hipLaunchKernelGGL(k_ekf_MS, dim3(nbM), dim3(kMSThreads), lds, s, P, ldp, N, H, ldh, r, n, hidx, sigma2, sc.M, Sup,
-                       nbM, sc.neg, Tall, sc.ldt, sc.kmask_tile);
-    hipLaunchKernelGGL(k_ekf_MS, dim3(nbS), dim3(kMSThreads), lds, s, P, ldp, N, H, ldh, r, n, hidx, sigma2, sc.M, Sup,
-                       0, (int *)nullptr, Tall, sc.ldt, sc.kmask_tile);
-    return;
-  }
   hipLaunchKernelGGL(k_ekf_MS, dim3(nbM + nbS), dim3(kMSThreads), lds, s, P, ldp, N, H, ldh, r, n, hidx, sigma2, sc.M, Sup,
-                     nbM, sc.neg, Tall, sc.ldt, Tall ? sc.kmask_tile : (const unsigned long long *)nullptr);
+                     nbM, sc.neg, sc.Tall, sc.ldt, sc.kmask_tile);
 }
 
 static void launch_ekf_factor(hipStream_t s, int N, int r, const double *res, int res_stride, EkfScratch &sc) {
@@ -583,16 +487,23 @@ void launch_ekf_phaseB(hipStream_t s, double *P, int ldp, int N, int r, const do
 // ---------------------------------------------------------------------------------------------------
 // One delayed-initialization candidate (StateHelper::initialize, StateHelper.cpp:393-577: initialize_invertible
 // of the landmark's 3 rows, then EKFUpdate of the other nup rows at the same factor that carries the chi2 test)
-// in six launches instead of eight (k_ekf_M_small, k_init_invertible, 2 x k_ekf_MS, k_ekf_fact, k_ekf_WP,
-// k_chain_apply):
-//   k_di_M    grid over the old state's 16-row blocks (rows < Ni): P[i, I] staged once; M_up = P[:, I] H_up^T on
-//             k_ekf_MS's tiles and M3 = P[:, I] H_init^T in k_ekf_M_small's GEMV order
-//   k_di_S    S_up from M_up's rows I (k_ekf_MS's gathered tile pairs); initialize_invertible (k_init_invertible's
-//             blocks: the landmark's cross-covariance columns and 3x3 block); the landmark's rows of M_up, from
-//             the same values k_init_invertible writes, on the tiles k_ekf_MS formed from P's new rows
-//   k_ekf_fact, k_ekf_WP, k_chain_apply unchanged
-// Every value is formed by the same expression, in the same order, as in the eight-launch chain (the old chain
-// stays behind UVIO_HP_DI_UNFUSED=1 for A/B runs; the 40-frame state digests of cfg3 and cfg3t are equal).
+// in six launches, the linearization (k_feature) before these five included; H holds the landmark's D
+// initializing rows H_init, then the nup update rows H_up:
+//   k_di_M    grid over the old state's 16-row blocks (rows < Ni), P[i, I] staged once in LDS:
+//             M_up = P[:, I] H_up^T (Ni x nup) on 16x16 MFMA tiles, one column tile per wave, ascending k;
+//             M3 = P[:, I] H_init^T (Ni x D) as a GEMV: one wavefront per row, lanes over the columns k (stride
+//             64, fma in ascending k), then a butterfly sum over the lanes (xor 32, 16, .. 1)
+//   k_di_S    three kinds of block:
+//             [0, nbG)        S_up = H_up T^T + s2 I with T^T = M_up's rows I: one upper tile pair per wave
+//             [nbG, nbG+nbX)  initialize_invertible: the landmark's cross-covariance columns -M3 H_Linv^T, 512
+//                             elements per block; the first block also its D x D block H_Linv (H_init M3[I] +
+//                             s2 I) H_Linv^T, each element of H_init M3[I] as 28 strided partials (k = j, j + 28,
+//                             ..) added in the fixed order j = 0 .. 27
+//             the last        the landmark's rows Ni .. Ni+D-1 of M_up: P's new rows recomputed from M3 by the
+//                             expression the blocks before it store, then the MFMA tiles of k_di_M
+//   k_ekf_fact, k_ekf_WP, k_chain_apply as in every other update
+// The arithmetic is StateHelper::initialize_invertible's and EKFUpdate's; these summation orders fix every bit of
+// the result (the 40-frame state digests of cfg3 and cfg3t), so they are not to be changed.
 // Measured and dropped: k_chain_apply folded into k_ekf_WP (the last workgroup to finish, after agent-scope
 // release / acquire fences around a completion counter, moving the tables): 22.8 us against 10.7 + 4.7 us.
 template <int D>
@@ -632,7 +543,7 @@ __global__ void __launch_bounds__(kMSThreads) k_di_M(const double *__restrict__ 
       if (row < Ni && col < nup) M[(size_t)row * nup + col] = acc[q];
     }
   }
-  // M3: one wavefront per row, lanes over the columns, butterfly sum (k_ekf_M_small)
+  // M3: one wavefront per row, lanes over the columns, butterfly sum
   for (int i = wid; i < 16 && i0 + i < Ni; i += kMSThreads / 64) {
     double acc[kSmallMRows] = {0.0, 0.0, 0.0, 0.0};
     for (int k = lane; k < n; k += 64) {
@@ -675,7 +586,7 @@ __global__ void __launch_bounds__(kMSThreads) k_di_S(double *__restrict__ P, int
   const double *Hup = H + D * (size_t)ldh;
   const int b = blockIdx.x;
   if (b < nbG) {
-    // S_up[a][b] = H_a T_b^T with T[b][k] = M[hidx[k]][b] (k_ekf_MS, ldt < 0)
+    // S_up[a][b] = H_a T_b^T with T[b][k] = M[hidx[k]][b] (as k_ekf_MS with ldt < 0)
     int *hs = (int *)sh;
     for (int k = threadIdx.x; k < n; k += blockDim.x) hs[k] = hidx[k];
     __syncthreads();
@@ -705,8 +616,8 @@ __global__ void __launch_bounds__(kMSThreads) k_di_S(double *__restrict__ P, int
   constexpr int DD = D * D;
   __shared__ double Hinv[DD], S3[DD], PLL[DD];
   if (b < nbG + nbX) {
-    // initialize_invertible (k_init_invertible with N = Ni: block xb takes the cross-covariance elements
-    // xb * 512 ..; the first one also the 3x3 block)
+    // initialize_invertible: block xb takes the cross-covariance elements xb * 512 ..; the first one also the
+    // D x D block
     const int xb = b - nbG, t = threadIdx.x + xb * kDiInitThreads;
     if (resout && xb == 0 && threadIdx.x < D) resout[threadIdx.x] = H[(size_t)threadIdx.x * ldh + n];
     if (gate && *gate == 0) return;
