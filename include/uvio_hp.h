@@ -363,13 +363,19 @@ int uvio_hp_debug_frame_feats(uvio_hp_t *h, int *kind, uint64_t *ids, double *pG
 /* StateHelper::EKFUpdate (StateHelper.cpp:116) on a standalone covariance: P (N x N, row-major,
  * in/out, host memory), H (r x n, row-major) whose column j maps to covariance index H_index[j]
  * (the H_order blocks flattened), residual (r), isotropic noise sigma2.  dx_out (N) receives K*res.
- * The update runs on the device (same kernels as the manager). */
+ * The update runs on the device (same kernels as the manager).
+ * Limits: r <= 255 rows (the factor panel holds the r rows of S and the residual row) and n <= 1215 columns
+ * (16 rows of P[:, H_index] staged in LDS); beyond either the call returns UVIO_HP_E_CAPACITY and touches
+ * nothing.  UVIO_HP_E_NUMERIC: the updated covariance has a negative diagonal entry (where the
+ * reference exits; P and dx_out hold the update all the same). */
 int uvio_hp_ekf_update(double *P, int N, const int *H_index, int n, const double *H, int r,
                        const double *res, double sigma2, double *dx_out);
 /* UpdaterMSCKF.cpp:274-286: measurement_compress_inplace of the stacked [H | res] (m x n) followed by
  * StateHelper::EKFUpdate on the compressed rows, on a standalone covariance (same arguments as
  * uvio_hp_ekf_update).  When m > n the device runs the update in information form on H^T H, H^T res
- * (the quantities the compressed system carries); otherwise it is uvio_hp_ekf_update. */
+ * (the quantities the compressed system carries); otherwise it is uvio_hp_ekf_update, with its limits.
+ * The information form takes any m and n <= 255 columns (its two factors are n and n + 1 rows of the
+ * 256-row panel); a wider H returns UVIO_HP_E_CAPACITY and touches nothing. */
 int uvio_hp_msckf_compressed_update(double *P, int N, const int *H_index, int n, const double *H, int m,
                                     const double *res, double sigma2, double *dx_out);
 /* UpdaterHelper::measurement_compress_inplace (UpdaterHelper.cpp:456) semantics: A = [H | res]

@@ -766,21 +766,28 @@ int Engine::ekf_update_standalone(double *P, int N, const int *H_index, int n, c
   if (!P || N <= 0 || n <= 0 || r <= 0 || !H || !res || !H_index || !dx_out) return UVIO_HP_E_ARG;
   for (int j = 0; j < n; j++)
     if (H_index[j] < 0 || H_index[j] >= N) return UVIO_HP_E_ARG;
+  // the limits the launchers would throw on, checked before anything is created: the factor panels hold 256 rows
+  // (the direct form's r rows and the information form's n columns, each with its augmented row), and k_ekf_MS
+  // stages 16 rows of P[:, I] in LDS
+  bool info = compress && r > n;
+  if (info ? n > kMaxEkfRows : r > kMaxEkfRows) return UVIO_HP_E_CAPACITY;
+  if (!info && (size_t)16 * (n | 1) * sizeof(double) > (size_t)kMaxDynLds) return UVIO_HP_E_CAPACITY;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return UVIO_HP_E_DEVICE;
   hipStream_t s;
   HP_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
   int ldh = n + 1;
-  bool info = compress && r > n;
-  if (!info && r > kMaxEkfRows) return UVIO_HP_E_CAPACITY;
   int rw = std::max(r, n + 1);
   int nch = gram_num_chunks(r);
   double *dP, *dH, *dM, *dW, *dS, *dy, *ddx, *dDinv, *dPart = nullptr, *dG = nullptr;
   int *dI, *dneg;
   dalloc(&dP, (size_t)N * N);
   dalloc(&dH, (size_t)r * ldh);
-  dalloc(&dM, (size_t)N * rw);
-  dalloc(&dW, (size_t)N * rw);
+  // M and W also serve as the (n + 1) x (n | 1) work matrices of the split information-form factors
+  // (launch_ekf_info_pre / _post), one row more than N when every state is measured (N == n)
+  const size_t mw = (size_t)std::max(N, n + 1) * rw;
+  dalloc(&dM, mw);
+  dalloc(&dW, mw);
   dalloc(&dS, (size_t)5 * rw * rw);
   dalloc(&dy, rw);
   dalloc(&dDinv, (size_t)(rw / 16 + 1) * 256);
