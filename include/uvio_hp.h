@@ -215,7 +215,12 @@ int uvio_hp_feed_imu_batch(uvio_hp_t *h, int n, const double *t, const double *w
 int uvio_hp_feed_simulation(uvio_hp_t *h, double t, int ncam, const int *cam_ids, const int *counts,
                             const uint64_t *ids, const float *uv);
 /* VioManager::feed_measurement_camera / UVioManager::feed_measurement_camera (UVioManager.h:48).
- * imgs[i] is a u8 W x H image with row stride strides[i]; masks may be NULL. */
+ * imgs[i] is a u8 W x H image with row stride strides[i]; masks may be NULL.
+ * W x H is the camera's configured size (with downsample_cameras the image is 2W x 2H).  No shape is refused:
+ * the sides need no divisibility, the cameras of one feed (a stereo pair included) may differ in size and
+ * so in pyramid depth, and strides[i] >= the image's width is the only requirement on the rows (E_ARG
+ * otherwise), with any alignment.  Tested from 31 x 31 and 90 x 30 up ("Image shapes");
+ * CLAHE needs sides >= 9, and a grid cell (W / grid_x by H / grid_y) below 7 x 7 pixels yields no corner. */
 int uvio_hp_feed_camera(uvio_hp_t *h, double t, int ncam, const int *cam_ids, const uint8_t *const *imgs,
                         const int *strides, const uint8_t *const *masks);
 /* The same with imgs[i] in device memory (HBM-resident input, e.g. a camera DMA buffer or a torch

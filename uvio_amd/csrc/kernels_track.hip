@@ -359,7 +359,10 @@ __global__ void __launch_bounds__(256) k_pyr_pair(PyrJob job, int l) {
   const int k5[5] = {1, 4, 6, 4, 1};
   for (int e = t; e < (T::QH + 2) * (T::QW + 2); e += 256) {
     const int ty = e / (T::QW + 2), tx = e - ty * (T::QW + 2);
-    const int x = reflect101(qx0 + tx - 1, dw), y = reflect101(qy0 + ty - 1, dh);
+    // Halo cells more than one past the level's edge (a partial tile) are read by nothing; they are held at the
+    // edge's cell, whose taps lie in the window: reflected further they leave it once the tile is less than half
+    // full (x0 = 64 of a 67-wide level: coordinate 64 of 34 reflects to 2, 58 window columns left of column 0)
+    const int x = reflect101(min(qx0 + tx - 1, dw), dw), y = reflect101(min(qy0 + ty - 1, dh), dh);
     int acc = 0;
 #pragma unroll
     for (int i = 0; i < 5; i++) {
