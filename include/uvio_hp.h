@@ -400,8 +400,9 @@ int uvio_hp_undistort(int model, const double cam[8], int n, const float *uv, fl
  * arrangement (off[ncell] ints) receives each cell's raster indices as libstdc++'s introsort loop leaves them
  * (std::sort's result is their stable order by response); for kmax in 1..64 top (ncell * kmax ints) receives the
  * first min(n, kmax) raster indices of the sorted cell (unused slots untouched).  depth < 0: the reference's
- * 2 lg n depth limit; 0 forces the heap-sort fallback (std::partial_sort(first, last, last)).  kmax 0: the whole
- * cell is arranged. */
+ * 2 lg n depth limit; 0 forces the heap-sort fallback (std::partial_sort(first, last, last)); a depth above 64,
+ * more than the kernel's segment stack can hold, is UVIO_HP_E_ARG (checked before any device call).  kmax 0: the
+ * whole cell is arranged. */
 int uvio_hp_debug_grid_order(const uint8_t *resp, const int *off, int ncell, int kmax, int depth, int *arrangement,
                              int *top);
 /* histogram_method 2 (TrackKLT.cpp:56-67, cv::createCLAHE(10.0, Size(8, 8))->apply) as the tracker runs it, on a

@@ -111,3 +111,20 @@ def test_tracks_bit_exact_dense_corners(euroc_yaml):
     assert intro > 0.5 * cells > 0
     assert total > 200
     assert bad == 0, (bad, total)
+
+
+def test_probe_depth_bound():
+    """one cell of four candidates: depth 65 is beyond the kernel's segment stack (UVIO_HP_E_ARG); 64, 0 and -1 are
+    accepted and give std::sort's order.  (At 16 candidates or fewer std::sort's introsort loop is never entered,
+    so no depth limit is looked at and the final insertion sort alone orders the cell: the heap-sort order that
+    test_probe_heap_sort_fallback asserts for depth 0 holds for cells above 16, as it selects them.)"""
+    from uvio_amd.manager import grid_order
+    from oracle import oracle as O
+    c = np.array([30, 25, 30, 22])
+    ref = O.grid_order(c.astype(np.float32), 0)
+    with pytest.raises(RuntimeError, match="E_ARG"):
+        grid_order([c], kmax=0, depth=65)
+    for depth in (64, 0, -1):
+        a = np.asarray(grid_order([c], kmax=0, depth=depth)[0][0])
+        assert sorted(a.tolist()) == [0, 1, 2, 3]
+        assert np.array_equal(a[np.argsort(-c[a], kind="stable")], ref), depth

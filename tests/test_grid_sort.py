@@ -242,3 +242,13 @@ def test_griding_keeps_std_sort_top_k(O):
             assert len(kp) > 16
             differ += list(order[:nfg]) != list(stable[:nfg])
     assert differ > 0
+
+
+def test_probe_refuses_depth_beyond_its_stack():
+    """uvio_hp_debug_grid_order with a depth limit above the kernel's 64-entry segment stack is UVIO_HP_E_ARG, found
+    in the argument checks: no device is needed to be told so (without one an accepted depth gets as far as
+    UVIO_HP_E_DEVICE)."""
+    from uvio_amd.manager import grid_order
+    cell = [np.array([30, 25, 30, 22])]
+    with pytest.raises(RuntimeError, match="E_ARG"):
+        grid_order(cell, kmax=0, depth=65)

@@ -321,32 +321,36 @@ struct ImuSample {
   double t, wm[3], am[3];
 };
 
-// Device-resident buffers (allocated once at create, sized from the config)
+// Device-resident buffers (allocated once at create, sized from the config).  The handles own their memory;
+// the raw pointers beside them are views into `chain` / `chain_host` or into the EKF scratch arrays.
 struct DeviceBufs {
-  hipStream_t stream = nullptr;
+  // the streams come first: members die in reverse order, so every buffer and event goes before the stream it was
+  // used on.  aux: the information-form prefactor's side stream (Engine::info_prefactor); copy: the staging uploads
+  Stream stream, aux, copy;
   int ldp = 0;               // P capacity / leading dimension
-  double *P = nullptr, *P2 = nullptr;
-  double *T = nullptr;       // propagation scratch (ldp x 64)
-  double *Phi = nullptr, *Q = nullptr, *dnc = nullptr;
-  int *iold = nullptr;
+  DevBuf<double> P, P2;
+  DevBuf<double> T;          // propagation scratch (ldp x 64)
+  DevBuf<double> Phi, Q, dnc;
+  DevBuf<int> iold;
   // update batch
   int max_feat = 0, max_meas_total = 0, max_vars_total = 0, max_rows = 0, ldh = 0, max_ncol = 0;
   DFeatOut *fout = nullptr;
-  double *chi2 = nullptr;
-  double *H = nullptr;       // H_all (max_rows x ldh)
-  double *Tall = nullptr;    // H_all P_can (max_rows x ldh), chi2 gate
-  double *chi2S = nullptr;   // per-feature S of the large chi2 gates (launch_chi2_batch grows it)
-  size_t chi2S_cap = 0;      // doubles
-  double *partials = nullptr;
-  double *R = nullptr;       // compressed (ncol x ncol, + global Cholesky scratch)
-  EkfScratch ekf{};
+  DevBuf<double> chi2;
+  DevBuf<double> H;          // H_all (max_rows x ldh)
+  DevBuf<double> Tall;       // H_all P_can (max_rows x ldh), chi2 gate
+  DevBuf<double> chi2S;      // per-feature S of the large chi2 gates (launch_chi2_batch grows it)
+  DevBuf<double> partials;
+  DevBuf<double> R;          // compressed (ncol x ncol, + global Cholesky scratch)
+  DevBuf<double> ekf_M, ekf_W, ekf_S, ekf_y, ekf_M3, ekf_Dinv;  // the arrays ekf's views point at
+  EkfScratch ekf{};          // passed by value to the launchers: views only (dx / neg lie in dxneg)
   // pinned mirrors of the results block (inside chain_host, below)
   double *dx_host = nullptr;
   int *neg_host = nullptr;
   DFeatOut *fout_host = nullptr;
   // upload staging ring: small host tables of one launch group are packed into pinned memory and sent
   // with ONE copy (stage / stage_flush); the kernels read the device copy directly
-  char *stg_h = nullptr, *stg_d = nullptr;
+  PinBuf<char> stg_h;
+  DevBuf<char> stg_d;
   size_t stg_cap = 0, stg_used = 0, stg_flushed = 0;
   long long stg_epoch = 0;  // ring restarts so far (a reservation must not outlive one: the chain checks)
   // [negative-diagonal count (8 B) | dx (cap + 15) | feature results (max features)], mirrored in pinned
@@ -354,21 +358,21 @@ struct DeviceBufs {
   double *dxneg = nullptr;
   size_t dx_bytes = 0;  // bytes of [count | dx] (the offset of the feature results)
   // feature sharding: the all-reduced [G upper triangle (max_ncol^2) | accepted features | accepted rows]
-  double *shard = nullptr, *shard_host = nullptr;
-  int *acc = nullptr;       // accepted features of the last update batch (gates its P update)
+  DevBuf<double> shard;
+  PinBuf<double> shard_host;  // created by shard_init_host
+  DevBuf<int> acc;          // accepted features of the last update batch (gates its P update)
   // information-form prefactor on a side stream (Engine::info_prefactor): P_II's factor and V while the
   // feature group runs; its column map in a dedicated device buffer (pinned mirror), the run it belongs to
-  hipStream_t aux = nullptr;
-  hipEvent_t ev_aux_in = nullptr, ev_aux_out = nullptr;
+  Event ev_aux_in, ev_aux_out;
   // staging uploads run on their own stream (the DMA transfer overlaps the kernels already queued on `stream`,
   // which waits on ev_copy before its next launch)
-  hipStream_t copy = nullptr;
-  hipEvent_t ev_copy = nullptr;
+  Event ev_copy;
   // the prefactor's column maps: kPreSlots pinned / device slots used in turn, each freed by its copy's event
   // (a slot is reused kPreSlots prefactors later, so the host never waits on the one just enqueued)
   static constexpr int kPreSlots = 8;
-  int *hidx_pre = nullptr, *hidx_pre_h = nullptr;
-  hipEvent_t ev_pre[kPreSlots] = {};
+  DevBuf<int> hidx_pre;
+  PinBuf<int> hidx_pre_h;
+  Event ev_pre[kPreSlots];
   int pre_slot = 0;
   std::vector<int> pre_hidx;  // columns of the pending prefactor (empty: none)
   int pre_N = -1;
@@ -379,17 +383,19 @@ struct DeviceBufs {
   // The chain's per-update regions sit right in front of dxneg (region r at dxneg - (r + 1) stride), and
   // chain_host mirrors [regions | dx block | fout] in pinned memory, so the chain's regions and every batch's
   // per-feature results come back in ONE copy (chain_results_copy)
-  double *chain = nullptr, *chain_host = nullptr;  // the allocations: [chain_k regions][dx block][fout]
+  DevBuf<char> chain;  // the allocations: [chain_k regions][dx block][fout]
+  PinBuf<char> chain_host;
   int chain_k = 0;
   size_t chain_stride = 0;
   double *region_dev(int r) const { return dxneg - (size_t)(r + 1) * chain_stride; }
   const double *region_host(int r) const { return (const double *)neg_host - (size_t)(r + 1) * chain_stride; }
   int fout_cap = 0;            // per-feature result slots in fout / fout_host (one frame chain's batches)
-  char *frame = nullptr;       // the frame chain's device state: clone / camera tables, pose values, mirror
+  DevBuf<char> frame;          // the frame chain's device state: clone / camera tables, pose values, mirror
   size_t frame_bytes = 0;
   // the chained UWB ranges of one message (Engine::uwb_update_message): per range a region [accepted, negative
   // diagonals, chi2, S | dx] of uwb_stride doubles (pinned mirror uwb_host) and its row h (16 doubles)
-  double *uwb_reg = nullptr, *uwb_host = nullptr, *uwb_h = nullptr;
+  DevBuf<double> uwb_reg, uwb_h;
+  PinBuf<double> uwb_host;
   size_t uwb_stride = 0;
 };
 
@@ -670,12 +676,14 @@ class Engine {
   // VioManager::retriangulate_active_tracks on the device (engine_retri.cpp)
   struct RetriState {
     int cap = 0, obs_cap = 0, slam_cap = 0, cur = 0, nslam = 0;
-    unsigned long long *keys[2] = {nullptr, nullptr};
-    DRetriEntry *ent[2] = {nullptr, nullptr};
-    DRetriObs *d_obs = nullptr, *h_obs = nullptr;
-    DRetriSlam *d_slam = nullptr, *h_slam = nullptr;
-    double *scratch = nullptr;
-    hipEvent_t copied = nullptr;
+    DevBuf<unsigned long long> keys[2];
+    DevBuf<DRetriEntry> ent[2];
+    DevBuf<DRetriObs> d_obs;
+    PinBuf<DRetriObs> h_obs;
+    DevBuf<DRetriSlam> d_slam;
+    PinBuf<DRetriSlam> h_slam;
+    DevBuf<double> scratch;
+    Event copied;
     bool copy_pending = false, valid = false;
     double time = -1;
     // the frame's job as taken at the reference's point (poses, landmarks, camera models, observations in

@@ -310,8 +310,10 @@ int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, s
     bp.tri_in = tri_in;
     bp.kmask = it.t_kmask;
     const char *tsdump = std::getenv("UVIO_HP_FEAT_TS");  // debug only: per-feature phase cycle counts
+    DevBuf<long long> dbg_ts;
     if (tsdump) {                                          // 8 k_feature + 4 k_chi2 stamps per feature
-      HP_HIP(hipMalloc(&bp.dbg_ts, sizeof(long long) * 16 * nf));
+      dbg_ts = DevBuf<long long>((size_t)16 * nf);
+      bp.dbg_ts = dbg_ts;
       HP_HIP(hipMemsetAsync(bp.dbg_ts, 0, sizeof(long long) * 16 * nf, d_.stream));
     }
     {
@@ -324,13 +326,12 @@ int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, s
       for (auto &F : b.feats) max_rows_f = std::max(max_rows_f, (mode == 0) ? 2 * F.nmeas - 3 : 2 * F.nmeas);
       KScope ks(&kprof_, KC_CHI2);
       launch_chi2_batch(d_.stream, bp, it.t_feats, d_.P, it.t_hidx, d_.H, b.rows, d_.Tall, d_.chi2, d_.fout + b.fout_off,
-                        max_rows_f, d_.acc, d_.R, &d_.chi2S, &d_.chi2S_cap, mode == 1);
+                        max_rows_f, d_.acc, d_.R, d_.chi2S, mode == 1);
     }
     if (tsdump) {  // synchronous copy-back: debug runs only (the chain loses its overlap)
       std::vector<long long> h(16 * (size_t)nf);
       HP_HIP(hipStreamSynchronize(d_.stream));
       HP_HIP(hipMemcpy(h.data(), bp.dbg_ts, sizeof(long long) * h.size(), hipMemcpyDeviceToHost));
-      HP_HIP(hipFree(bp.dbg_ts));
       if (FILE *fp = std::fopen(tsdump, "ab")) {
         for (int i = 0; i < nf; i++) {
           long long rec[16] = {mode, nf, b.feats[i].nmeas, b.feats[i].nf};
@@ -554,8 +555,10 @@ int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, s
       const int Ni = N0 + d * j, nup = 2 * F.nmeas - 3, Nn = Ni + d;
       bp.tri_in = tri_out + j;
       const char *tsdump = std::getenv("UVIO_HP_FEAT_TS");  // debug only: the candidate's phase cycle counts
+      DevBuf<long long> dbg_ts;
       if (tsdump) {
-        HP_HIP(hipMalloc(&bp.dbg_ts, sizeof(long long) * 16));
+        dbg_ts = DevBuf<long long>(16);
+        bp.dbg_ts = dbg_ts;
         HP_HIP(hipMemsetAsync(bp.dbg_ts, 0, sizeof(long long) * 16, d_.stream));
       }
       {
@@ -567,8 +570,8 @@ int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, s
         long long h[16];
         HP_HIP(hipStreamSynchronize(d_.stream));
         HP_HIP(hipMemcpy(h, bp.dbg_ts, sizeof(h), hipMemcpyDeviceToHost));
-        HP_HIP(hipFree(bp.dbg_ts));
         bp.dbg_ts = nullptr;
+        dbg_ts.reset();  // as before, ahead of the candidate's remaining launches
         if (FILE *fp = std::fopen(tsdump, "ab")) {
           long long rec[16] = {3, 1, F.nmeas, F.nf};
           for (int k = 0; k < 12; k++) rec[4 + k] = h[k];

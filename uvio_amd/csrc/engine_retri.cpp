@@ -23,16 +23,16 @@ void Engine::retri_alloc(int nobs, int nslam) {
   const int ns = std::max(nslam, 1);
   int need = 1024;
   while (need < 2 * std::max(nobs, 1)) need *= 2;
-  // buffers the auxiliary stream may still read are replaced only after it has drained
+  // buffers the auxiliary stream may still read are replaced only after it has drained; each is reset before its
+  // replacement is allocated (the peak stays one copy, and a failed allocation leaves an empty handle)
   if (nobs > rt_.obs_cap || need > rt_.cap || ns > rt_.slam_cap) HP_HIP(hipStreamSynchronize(d_.aux));
   if (nobs > rt_.obs_cap) {
     const int oc = std::max(nobs, 2 * rt_.obs_cap);
-    if (rt_.d_obs) HP_HIP(hipFree(rt_.d_obs));
-    if (rt_.h_obs) HP_HIP(hipHostFree(rt_.h_obs));
-    if (rt_.scratch) HP_HIP(hipFree(rt_.scratch));
-    HP_HIP(hipMalloc(&rt_.d_obs, sizeof(DRetriObs) * oc));
-    HP_HIP(hipHostMalloc(&rt_.h_obs, sizeof(DRetriObs) * oc, hipHostMallocDefault));
-    HP_HIP(hipMalloc(&rt_.scratch, sizeof(double) * 17 * oc));
+    rt_.obs_cap = 0;
+    rt_.d_obs.reset(), rt_.h_obs.reset(), rt_.scratch.reset();
+    rt_.d_obs = DevBuf<DRetriObs>(oc);
+    rt_.h_obs = PinBuf<DRetriObs>(oc);
+    rt_.scratch = DevBuf<double>((size_t)17 * oc);
     rt_.obs_cap = oc;
   }
   if (need > rt_.cap) {
@@ -47,11 +47,11 @@ void Engine::retri_alloc(int nobs, int nslam) {
       HP_HIP(hipMemcpy(keys.data(), rt_.keys[rt_.cur], sizeof(unsigned long long) * rt_.cap, hipMemcpyDeviceToHost));
       HP_HIP(hipMemcpy(ent.data(), rt_.ent[rt_.cur], sizeof(DRetriEntry) * rt_.cap, hipMemcpyDeviceToHost));
     }
+    rt_.cap = 0;  // (as obs_cap above) a throw below leaves the capacity that the empty handles have
     for (int g = 0; g < 2; g++) {
-      if (rt_.keys[g]) HP_HIP(hipFree(rt_.keys[g]));
-      if (rt_.ent[g]) HP_HIP(hipFree(rt_.ent[g]));
-      HP_HIP(hipMalloc(&rt_.keys[g], sizeof(unsigned long long) * need));
-      HP_HIP(hipMalloc(&rt_.ent[g], sizeof(DRetriEntry) * need));
+      rt_.keys[g].reset(), rt_.ent[g].reset();
+      rt_.keys[g] = DevBuf<unsigned long long>(need);
+      rt_.ent[g] = DevBuf<DRetriEntry>(need);
       HP_HIP(hipMemset(rt_.keys[g], 0xFF, sizeof(unsigned long long) * need));
     }
     if (!keys.empty()) {
@@ -74,10 +74,10 @@ void Engine::retri_alloc(int nobs, int nslam) {
     rt_.cap = need;
   }
   if (ns > rt_.slam_cap) {
-    if (rt_.d_slam) HP_HIP(hipFree(rt_.d_slam));
-    if (rt_.h_slam) HP_HIP(hipHostFree(rt_.h_slam));
-    HP_HIP(hipMalloc(&rt_.d_slam, sizeof(DRetriSlam) * 2 * ns));
-    HP_HIP(hipHostMalloc(&rt_.h_slam, sizeof(DRetriSlam) * 2 * ns, hipHostMallocDefault));
+    rt_.slam_cap = 0;
+    rt_.d_slam.reset(), rt_.h_slam.reset();
+    rt_.d_slam = DevBuf<DRetriSlam>((size_t)2 * ns);
+    rt_.h_slam = PinBuf<DRetriSlam>((size_t)2 * ns);
     rt_.slam_cap = 2 * ns;
   }
 }

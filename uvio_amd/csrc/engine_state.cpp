@@ -176,39 +176,9 @@ Engine::Engine(const uvio_hp_options_t &o, int device) : o_(o), device_(device) 
 
 Engine::~Engine() {
   if (timing_csv_) std::fclose(timing_csv_);
-  hipSetDevice(device_);
-  if (shard_.nccl) rccl_comm_destroy(shard_.nccl);
+  hipSetDevice(device_);  // the members' destructors run after this body: every free happens on this device
+  if (shard_.nccl) rccl_comm_destroy(shard_.nccl);  // before the stream it used
   tracker_.reset();
-  void *rptrs[] = {rt_.keys[0], rt_.keys[1], rt_.ent[0], rt_.ent[1], rt_.d_obs, rt_.d_slam, rt_.scratch};
-  for (void *p : rptrs)
-    if (p) hipFree(p);
-  if (rt_.h_obs) hipHostFree(rt_.h_obs);
-  if (rt_.h_slam) hipHostFree(rt_.h_slam);
-  if (rt_.copied) hipEventDestroy(rt_.copied);
-  void *ptrs[] = {d_.P, d_.P2, d_.T, d_.Phi, d_.Q, d_.dnc, d_.iold,
-                  d_.chi2, d_.H, d_.Tall, d_.partials, d_.R, d_.ekf.M, d_.ekf.W, d_.ekf.S, d_.ekf.y,
-                  d_.ekf.Dinv, d_.stg_d, d_.acc, d_.shard, d_.hidx_pre, d_.chain, d_.frame, d_.chi2S, d_.uwb_reg,
-                  d_.uwb_h};
-  for (void *p : ptrs)
-    if (p) hipFree(p);
-  if (d_.shard_host) hipHostFree(d_.shard_host);
-  if (d_.stg_h) hipHostFree(d_.stg_h);
-  if (d_.hidx_pre_h) hipHostFree(d_.hidx_pre_h);
-  if (d_.chain_host) hipHostFree(d_.chain_host);
-  if (d_.uwb_host) hipHostFree(d_.uwb_host);
-  for (auto &e : d_.ev_pre)
-    if (e) hipEventDestroy(e);
-  if (d_.ev_aux_in) hipEventDestroy(d_.ev_aux_in);
-  if (d_.ev_aux_out) hipEventDestroy(d_.ev_aux_out);
-  if (d_.aux) hipStreamDestroy(d_.aux);
-  if (d_.ev_copy) hipEventDestroy(d_.ev_copy);
-  if (d_.copy) hipStreamDestroy(d_.copy);
-  if (d_.stream) hipStreamDestroy(d_.stream);
-}
-
-template <typename T>
-static void dalloc(T **p, size_t n) {
-  HP_HIP(hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T)));
 }
 
 // Capacities from the config (DESIGN.md "Data layout"): P is sized for the largest state the
@@ -219,27 +189,27 @@ void Engine::alloc_device() {
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device_)
     throw HpError(UVIO_HP_E_DEVICE, "no HIP device " + std::to_string(device_));
   HP_HIP(hipSetDevice(device_));
-  HP_HIP(hipStreamCreateWithFlags(&d_.stream, hipStreamNonBlocking));
-  HP_HIP(hipStreamCreateWithFlags(&d_.aux, hipStreamNonBlocking));
-  HP_HIP(hipEventCreateWithFlags(&d_.ev_aux_in, hipEventDisableTiming));
-  HP_HIP(hipEventCreateWithFlags(&d_.ev_aux_out, hipEventDisableTiming));
-  HP_HIP(hipStreamCreateWithFlags(&d_.copy, hipStreamNonBlocking));
-  HP_HIP(hipEventCreateWithFlags(&d_.ev_copy, hipEventDisableTiming));
+  d_.stream = Stream::create();
+  d_.aux = Stream::create();
+  d_.ev_aux_in = Event::create();
+  d_.ev_aux_out = Event::create();
+  d_.copy = Stream::create();
+  d_.ev_copy = Event::create();
   kprof_.stream = d_.stream;
-  HP_HIP(hipEventCreateWithFlags(&rt_.copied, hipEventDisableTiming));
+  rt_.copied = Event::create();
   d_.ekf.kp = &kprof_;
   int C = o_.max_clone_size + 2;
   int K = o_.num_cameras;
   int cap = N_ + 6 * C + 3 * std::max(o_.max_slam_features, 0) + 5 * UVIO_HP_MAX_ANCHORS + 3 + 8;
   cap = (cap + 7) / 8 * 8;
   d_.ldp = cap;
-  dalloc(&d_.P, (size_t)cap * cap);
-  dalloc(&d_.P2, (size_t)cap * cap);
-  dalloc(&d_.T, (size_t)cap * 64);
-  dalloc(&d_.Phi, 64 * 64);
-  dalloc(&d_.Q, 64 * 64);
-  dalloc(&d_.dnc, 8);
-  dalloc(&d_.iold, 256);
+  d_.P = DevBuf<double>((size_t)cap * cap);
+  d_.P2 = DevBuf<double>((size_t)cap * cap);
+  d_.T = DevBuf<double>((size_t)cap * 64);
+  d_.Phi = DevBuf<double>(64 * 64);
+  d_.Q = DevBuf<double>(64 * 64);
+  d_.dnc = DevBuf<double>(8);
+  d_.iold = DevBuf<int>(256);
   // update batch capacities
   int maxf = std::max(o_.max_msckf_in_update, 1);
   maxf = std::min(maxf, 4096);
@@ -252,23 +222,22 @@ void Engine::alloc_device() {
   d_.max_rows = maxf * 2 * meas_per_feat;
   d_.max_ncol = cap + 1;
   d_.ldh = (d_.max_ncol + 7) / 8 * 8;
-  dalloc(&d_.chi2, 1000);
-  dalloc(&d_.H, (size_t)d_.max_rows * d_.ldh);
-  dalloc(&d_.Tall, (size_t)d_.max_rows * d_.ldh);
+  d_.chi2 = DevBuf<double>(1000);
+  d_.H = DevBuf<double>((size_t)d_.max_rows * d_.ldh);
+  d_.Tall = DevBuf<double>((size_t)d_.max_rows * d_.ldh);
   int maxch = std::max((d_.max_rows + 511) / 512 + 1, gram_num_chunks(2048) + 1);  // 512- or 64-row chunks
-  dalloc(&d_.partials, (size_t)maxch * d_.max_ncol * d_.max_ncol);
-  dalloc(&d_.R, (size_t)2 * d_.max_ncol * d_.ldh);
-  dalloc(&d_.hidx_pre, (size_t)DeviceBufs::kPreSlots * d_.max_ncol);
-  HP_HIP(hipHostMalloc((void **)&d_.hidx_pre_h, sizeof(int) * DeviceBufs::kPreSlots * std::max(d_.max_ncol, 1),
-                       hipHostMallocDefault));
-  for (auto &e : d_.ev_pre) HP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  d_.partials = DevBuf<double>((size_t)maxch * d_.max_ncol * d_.max_ncol);
+  d_.R = DevBuf<double>((size_t)2 * d_.max_ncol * d_.ldh);
+  d_.hidx_pre = DevBuf<int>((size_t)DeviceBufs::kPreSlots * d_.max_ncol);
+  d_.hidx_pre_h = PinBuf<int>((size_t)DeviceBufs::kPreSlots * d_.max_ncol);
+  for (auto &e : d_.ev_pre) e = Event::create();
   int rmax = std::max(d_.max_ncol, kMaxEkfRows);
-  dalloc(&d_.ekf.M, (size_t)cap * rmax);
-  dalloc(&d_.ekf.W, (size_t)cap * rmax);
-  dalloc(&d_.ekf.S, (size_t)5 * rmax * rmax);
-  dalloc(&d_.ekf.y, rmax);
-  dalloc(&d_.ekf.M3, (size_t)cap * 3);
-  dalloc(&d_.ekf.Dinv, (size_t)(rmax / 16 + 1) * 256);
+  d_.ekf.M = d_.ekf_M = DevBuf<double>((size_t)cap * rmax);
+  d_.ekf.W = d_.ekf_W = DevBuf<double>((size_t)cap * rmax);
+  d_.ekf.S = d_.ekf_S = DevBuf<double>((size_t)5 * rmax * rmax);
+  d_.ekf.y = d_.ekf_y = DevBuf<double>(rmax);
+  d_.ekf.M3 = d_.ekf_M3 = DevBuf<double>((size_t)cap * 3);
+  d_.ekf.Dinv = d_.ekf_Dinv = DevBuf<double>((size_t)(rmax / 16 + 1) * 256);
   d_.dx_bytes = sizeof(double) * (cap + 16);
   // One chain holds the MSCKF batch (at most maxf features, one region), the SLAM chunks (a result slot per
   // landmark, at most a region each) and the delayed initialization's two passes (two slots and one region per
@@ -281,15 +250,15 @@ void Engine::alloc_device() {
   // [chain regions (reversed) | dx block (neg, dx) | fout] on the device and mirrored in pinned memory
   const size_t reg_bytes = sizeof(double) * d_.chain_k * d_.chain_stride;
   const size_t res_bytes = reg_bytes + d_.dx_bytes + sizeof(DFeatOut) * d_.fout_cap;
-  HP_HIP(hipMalloc((void **)&d_.chain, res_bytes));
+  d_.chain = DevBuf<char>(res_bytes);
   HP_HIP(hipMemset(d_.chain, 0, res_bytes));
   d_.dxneg = (double *)((char *)d_.chain + reg_bytes);
   d_.fout = (DFeatOut *)((char *)d_.dxneg + d_.dx_bytes);
-  dalloc(&d_.acc, 4);
-  dalloc(&d_.shard, (size_t)d_.max_ncol * d_.max_ncol + 2);
+  d_.acc = DevBuf<int>(4);
+  d_.shard = DevBuf<double>((size_t)d_.max_ncol * d_.max_ncol + 2);
   d_.ekf.neg = (int *)d_.dxneg;
   d_.ekf.dx = d_.dxneg + 1;
-  HP_HIP(hipHostMalloc((void **)&d_.chain_host, res_bytes + 64, hipHostMallocDefault));
+  d_.chain_host = PinBuf<char>(res_bytes + 64);
   // chi2 table: boost::math::quantile(chi_squared(dof), 0.95) for dof 1..999 (UpdaterMSCKF.cpp:52-55)
   for (int i = 1; i < 1000; i++) chi2_table_[i] = chi2_quantile95(i);
   HP_HIP(hipMemcpy(d_.chi2, chi2_table_.data(), 1000 * sizeof(double), hipMemcpyHostToDevice));
@@ -301,7 +270,7 @@ void Engine::alloc_device() {
   const int maxcl = cap / 6;
   d_.frame_bytes = sizeof(DClone) * maxcl + sizeof(DCam) * UVIO_HP_MAX_CAMS + sizeof(DPoseVal) * (maxcl + UVIO_HP_MAX_CAMS) +
                    sizeof(double) * cap + 1024;
-  dalloc(&d_.frame, d_.frame_bytes);
+  d_.frame = DevBuf<char>(d_.frame_bytes);
   // upload staging ring (batch tables, Phi / Q, column maps): one full update batch's tables and some slack
   const size_t batch_bytes =
       sizeof(DFeat) * maxf + sizeof(DMeas) * d_.max_meas_total + sizeof(DVar) * d_.max_vars_total +
@@ -312,12 +281,12 @@ void Engine::alloc_device() {
   // test hook: a smaller ring recycles every few batches (tests/test_gpu_configs.py staging test)
   if (const char *e = std::getenv("UVIO_HP_STAGE_BYTES")) d_.stg_cap = std::min(d_.stg_cap, (size_t)std::atoll(e));
   if (const char *e = std::getenv("UVIO_HP_NO_PREDETECT")) predetect_on_ = e[0] != '1';
-  HP_HIP(hipHostMalloc(&d_.stg_h, d_.stg_cap, hipHostMallocDefault));
-  HP_HIP(hipMalloc(&d_.stg_d, d_.stg_cap));
+  d_.stg_h = PinBuf<char>(d_.stg_cap);
+  d_.stg_d = DevBuf<char>(d_.stg_cap);
   d_.uwb_stride = (size_t)d_.ldp + 4;
-  dalloc(&d_.uwb_reg, kUwbMaxRanges * d_.uwb_stride);
-  dalloc(&d_.uwb_h, kUwbMaxRanges * 16);
-  HP_HIP(hipHostMalloc((void **)&d_.uwb_host, sizeof(double) * kUwbMaxRanges * d_.uwb_stride, hipHostMallocDefault));
+  d_.uwb_reg = DevBuf<double>(kUwbMaxRanges * d_.uwb_stride);
+  d_.uwb_h = DevBuf<double>(kUwbMaxRanges * 16);
+  d_.uwb_host = PinBuf<double>(kUwbMaxRanges * d_.uwb_stride);
 }
 
 void Engine::upload_P_full(const std::vector<double> &Ph, int N) {
@@ -774,30 +743,21 @@ int Engine::ekf_update_standalone(double *P, int N, const int *H_index, int n, c
   if (!info && (size_t)16 * (n | 1) * sizeof(double) > (size_t)kMaxDynLds) return UVIO_HP_E_CAPACITY;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return UVIO_HP_E_DEVICE;
-  hipStream_t s;
-  HP_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  Stream s = Stream::create();
   int ldh = n + 1;
   int rw = std::max(r, n + 1);
   int nch = gram_num_chunks(r);
-  double *dP, *dH, *dM, *dW, *dS, *dy, *ddx, *dDinv, *dPart = nullptr, *dG = nullptr;
-  int *dI, *dneg;
-  dalloc(&dP, (size_t)N * N);
-  dalloc(&dH, (size_t)r * ldh);
+  DevBuf<double> dP((size_t)N * N), dH((size_t)r * ldh);
   // M and W also serve as the (n + 1) x (n | 1) work matrices of the split information-form factors
   // (launch_ekf_info_pre / _post), one row more than N when every state is measured (N == n)
   const size_t mw = (size_t)std::max(N, n + 1) * rw;
-  dalloc(&dM, mw);
-  dalloc(&dW, mw);
-  dalloc(&dS, (size_t)5 * rw * rw);
-  dalloc(&dy, rw);
-  dalloc(&dDinv, (size_t)(rw / 16 + 1) * 256);
+  DevBuf<double> dM(mw), dW(mw), dS((size_t)5 * rw * rw), dy(rw), dDinv((size_t)(rw / 16 + 1) * 256), dPart, dG;
   if (info) {
-    dalloc(&dPart, (size_t)nch * ldh * ldh);
-    dalloc(&dG, (size_t)ldh * ldh);
+    dPart = DevBuf<double>((size_t)nch * ldh * ldh);
+    dG = DevBuf<double>((size_t)ldh * ldh);
   }
-  dalloc(&ddx, N);
-  dalloc(&dI, n);
-  dalloc(&dneg, 2 + n);
+  DevBuf<double> ddx(N);
+  DevBuf<int> dI(n), dneg(2 + n);
   std::vector<double> Ha((size_t)r * ldh);
   for (int i = 0; i < r; i++) {
     std::memcpy(&Ha[(size_t)i * ldh], H + (size_t)i * n, sizeof(double) * n);
@@ -819,11 +779,7 @@ int Engine::ekf_update_standalone(double *P, int N, const int *H_index, int n, c
   HP_HIP(hipMemcpyAsync(P, dP, sizeof(double) * N * N, hipMemcpyDeviceToHost, s));
   HP_HIP(hipMemcpyAsync(dx_out, ddx, sizeof(double) * N, hipMemcpyDeviceToHost, s));
   HP_HIP(hipMemcpyAsync(&neg, dneg, sizeof(int), hipMemcpyDeviceToHost, s));
-  HP_HIP(hipStreamSynchronize(s));
-  void *ptrs[] = {dP, dH, dM, dW, dS, dy, ddx, dDinv, dI, dneg, dPart, dG};
-  for (void *p : ptrs)
-    if (p) hipFree(p);
-  hipStreamDestroy(s);
+  HP_HIP(hipStreamSynchronize(s));  // nothing in flight when the buffers go (on a throw: freeing device memory waits by itself)
   return neg > 0 ? UVIO_HP_E_NUMERIC : 0;
 }
 
@@ -832,27 +788,18 @@ int Engine::compress_standalone(const double *A, int m, int n, double *R_out) {
   if (!A || m <= 0 || n <= 0 || !R_out) return UVIO_HP_E_ARG;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return UVIO_HP_E_DEVICE;
-  hipStream_t s;
-  HP_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  Stream s = Stream::create();
   int ncol = n + 1;
   int nch = gram_num_chunks(m);
-  double *dA, *dPart, *dR;
-  dalloc(&dA, (size_t)m * ncol);
-  dalloc(&dPart, (size_t)nch * ncol * ncol);
-  dalloc(&dR, (size_t)2 * ncol * ncol);
+  DevBuf<double> dA((size_t)m * ncol), dPart((size_t)nch * ncol * ncol), dR((size_t)2 * ncol * ncol);
   HP_HIP(hipMemcpyAsync(dA, A, sizeof(double) * m * ncol, hipMemcpyHostToDevice, s));
   int nc2 = 0;
   launch_gram(s, dA, m, ncol, ncol, dPart, &nc2);
   launch_gram_reduce_chol(s, dPart, nc2, ncol, dR, ncol);
   HP_HIP(hipMemcpyAsync(R_out, dR, sizeof(double) * ncol * ncol, hipMemcpyDeviceToHost, s));
-  HP_HIP(hipStreamSynchronize(s));
-  hipFree(dA);
-  hipFree(dPart);
-  hipFree(dR);
-  hipStreamDestroy(s);
+  HP_HIP(hipStreamSynchronize(s));  // nothing in flight when the buffers go (on a throw: freeing device memory waits by itself)
   return 0;
 }
-
 
 // CamBase::undistort_f (ov_core/src/cam/CamBase.h:89, CamRadtan.h:99 / CamEqui.h:108) over n points on the
 // device; the points whose float result could depend on the equidistant model's tan (cam_undistort_f's flag)
@@ -865,23 +812,15 @@ int Engine::undistort_standalone(int model, const double cam[8], int n, const fl
   CamParams c{};
   c.model = model;
   for (int k = 0; k < 8; k++) c.v[k] = cam[k];
-  hipStream_t s;
-  HP_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  float *d_uv, *d_uvn;
-  uint8_t *d_amb;
-  HP_HIP(hipMalloc(&d_uv, sizeof(float) * 2 * (size_t)n));
-  HP_HIP(hipMalloc(&d_uvn, sizeof(float) * 2 * (size_t)n));
-  HP_HIP(hipMalloc(&d_amb, (size_t)n));
+  Stream s = Stream::create();
+  DevBuf<float> d_uv(2 * (size_t)n), d_uvn(2 * (size_t)n);
+  DevBuf<uint8_t> d_amb(n);
   std::vector<uint8_t> h_amb(n);
   HP_HIP(hipMemcpyAsync(d_uv, uv, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, s));
   launch_undistort_points(s, c, n, d_uv, d_uvn, d_amb);
   HP_HIP(hipMemcpyAsync(uvn, d_uvn, sizeof(float) * 2 * (size_t)n, hipMemcpyDeviceToHost, s));
   HP_HIP(hipMemcpyAsync(h_amb.data(), d_amb, (size_t)n, hipMemcpyDeviceToHost, s));
-  HP_HIP(hipStreamSynchronize(s));
-  hipFree(d_uv);
-  hipFree(d_uvn);
-  hipFree(d_amb);
-  hipStreamDestroy(s);
+  HP_HIP(hipStreamSynchronize(s));  // nothing in flight when the buffers go (on a throw: freeing device memory waits by itself)
   for (int i = 0; i < n; i++) {
     if (h_amb[i]) cam_undistort_f(c, uv[2 * i], uv[2 * i + 1], uvn[2 * i], uvn[2 * i + 1]);
     if (amb) amb[i] = h_amb[i];
@@ -892,6 +831,7 @@ int Engine::undistort_standalone(int model, const double cam[8], int n, const fl
 int Engine::grid_order_standalone(const uint8_t *resp, const int *off, int ncell, int kmax, int depth,
                                   int *arrangement, int *top) {
   if (ncell < 0 || !off || kmax < 0 || kmax > 64 || (kmax > 0 && !top)) return UVIO_HP_E_ARG;
+  if (depth > kSortStack) return UVIO_HP_E_ARG;  // every level of the depth limit may leave a segment on the stack
   if (ncell == 0) return 0;
   int nmax = 0;
   for (int c = 0; c < ncell; c++) {
@@ -903,15 +843,10 @@ int Engine::grid_order_standalone(const uint8_t *resp, const int *off, int ncell
   if (nmax > 16384) return UVIO_HP_E_CAPACITY;  // 8 bytes of LDS per candidate
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return UVIO_HP_E_DEVICE;
-  hipStream_t s;
-  HP_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  uint8_t *d_resp = nullptr;
-  int *d_off = nullptr, *d_arr = nullptr, *d_top = nullptr;
+  Stream s = Stream::create();
   const size_t ntop = (size_t)ncell * (size_t)std::max(kmax, 1);
-  HP_HIP(hipMalloc(&d_resp, std::max(total, 1)));
-  HP_HIP(hipMalloc(&d_off, sizeof(int) * (size_t)(ncell + 1)));
-  HP_HIP(hipMalloc(&d_arr, sizeof(int) * (size_t)std::max(total, 1)));
-  HP_HIP(hipMalloc(&d_top, sizeof(int) * ntop));
+  DevBuf<uint8_t> d_resp(total);
+  DevBuf<int> d_off((size_t)ncell + 1), d_arr(total), d_top(ntop);
   if (total > 0) HP_HIP(hipMemcpyAsync(d_resp, resp, (size_t)total, hipMemcpyHostToDevice, s));
   HP_HIP(hipMemcpyAsync(d_off, off, sizeof(int) * (size_t)(ncell + 1), hipMemcpyHostToDevice, s));
   if (kmax > 0) HP_HIP(hipMemcpyAsync(d_top, top, sizeof(int) * ntop, hipMemcpyHostToDevice, s));
@@ -919,38 +854,9 @@ int Engine::grid_order_standalone(const uint8_t *resp, const int *off, int ncell
   HP_HIP(hipGetLastError());
   if (total > 0) HP_HIP(hipMemcpyAsync(arrangement, d_arr, sizeof(int) * (size_t)total, hipMemcpyDeviceToHost, s));
   if (kmax > 0) HP_HIP(hipMemcpyAsync(top, d_top, sizeof(int) * ntop, hipMemcpyDeviceToHost, s));
-  HP_HIP(hipStreamSynchronize(s));
-  hipFree(d_resp);
-  hipFree(d_off);
-  hipFree(d_arr);
-  hipFree(d_top);
-  hipStreamDestroy(s);
+  HP_HIP(hipStreamSynchronize(s));  // nothing in flight when the buffers go (on a throw: freeing device memory waits by itself)
   return 0;
 }
-
-namespace {
-// a standalone probe's stream and device buffers, released on every way out of its scope
-struct ProbeScope {
-  hipStream_t s = nullptr;
-  std::vector<void *> bufs;
-  ProbeScope() { HP_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
-  ProbeScope(const ProbeScope &) = delete;
-  ProbeScope &operator=(const ProbeScope &) = delete;
-  ~ProbeScope() {
-    if (s) (void)hipStreamSynchronize(s);  // nothing in flight on a buffer freed below
-    for (void *p : bufs) (void)hipFree(p);
-    if (s) (void)hipStreamDestroy(s);
-  }
-  template <class T>
-  T *alloc(size_t n) {
-    void *p = nullptr;
-    bufs.reserve(bufs.size() + 1);  // a failed push_back cannot strand the allocation
-    HP_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
-    bufs.push_back(p);
-    return (T *)p;
-  }
-};
-}  // namespace
 
 // histogram_method 2 on a caller-given image: the tracker's own launch_pyramids on a one-level pyramid
 int Engine::clahe_standalone(const uint8_t *img, int w, int h, int stride, uint8_t *out) {
@@ -959,9 +865,9 @@ int Engine::clahe_standalone(const uint8_t *img, int w, int h, int stride, uint8
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return UVIO_HP_E_DEVICE;
   const size_t n = (size_t)w * h;
-  ProbeScope ps;
-  uint8_t *d_src = ps.alloc<uint8_t>(n), *d_img = ps.alloc<uint8_t>(n);
-  int16_t *d_der = ps.alloc<int16_t>(2 * n);
+  Stream s = Stream::create();
+  DevBuf<uint8_t> d_src(n), d_img(n), d_lut(kClaheLutBytes);
+  DevBuf<int16_t> d_der(2 * n);
   PyrJob job{};
   job.ncam = 1;
   job.method = 2;
@@ -972,12 +878,12 @@ int Engine::clahe_standalone(const uint8_t *img, int w, int h, int stride, uint8
   job.p[0].der[0] = d_der;
   job.src[0] = d_src;
   job.stride[0] = w;
-  job.clahe[0] = ps.alloc<uint8_t>(kClaheLutBytes);
-  HP_HIP(hipMemcpy2DAsync(d_src, w, img, stride, w, h, hipMemcpyHostToDevice, ps.s));
-  launch_pyramids(ps.s, job);
+  job.clahe[0] = d_lut;
+  HP_HIP(hipMemcpy2DAsync(d_src, w, img, stride, w, h, hipMemcpyHostToDevice, s));
+  launch_pyramids(s, job);
   HP_HIP(hipGetLastError());
-  HP_HIP(hipMemcpyAsync(out, d_img, n, hipMemcpyDeviceToHost, ps.s));
-  HP_HIP(hipStreamSynchronize(ps.s));
+  HP_HIP(hipMemcpyAsync(out, d_img, n, hipMemcpyDeviceToHost, s));
+  HP_HIP(hipStreamSynchronize(s));  // nothing in flight when the buffers go (on a throw: freeing device memory waits by itself)
   return 0;
 }
 

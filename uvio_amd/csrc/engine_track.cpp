@@ -88,7 +88,8 @@ struct Occupancy {  // cv::Mat grid_2d_close / grid_2d_grid (CV_8UC1)
 
 struct Tracker::Bufs {
   int cap = 0, maxcells = 0, kmax = 0;
-  char *dmem = nullptr, *hmem = nullptr;
+  DevBuf<char> dmem;  // the typed pointers below are views into it
+  PinBuf<char> hmem;
   size_t mirror = 0;  // bytes [0, mirror) of the device block are mirrored in pinned host memory
   // device (host mirror: hp(x)); the matching inputs [p0 | sub] x kMaxCams slots and outputs
   // [p1 | st | mask | amb | p1n] x kMaxCams are contiguous so each direction is one copy per frame
@@ -145,7 +146,7 @@ Tracker::Tracker(const uvio_hp_options_t &o, const CamParams *cams, hipStream_t 
       spmask_host_[(size_t)i * ww + j] = (float)(vy * std::exp(-x * x));
     }
   }
-  b_ = new Bufs();
+  b_.reset(new Bufs());
   b_->maxcells = grid_x_ * grid_y_;
   int gx = grid_x_, gy = grid_y_;
   if (num_features_ < gx * gy) {
@@ -155,9 +156,9 @@ Tracker::Tracker(const uvio_hp_options_t &o, const CamParams *cams, hipStream_t 
   }
   b_->kmax = (int)((double)num_features_ / (double)(gx * gy)) + 1;
   ensure_cap(std::max(1024, 8 * num_features_));
-  HP_HIP(hipMalloc(&d_lk_bytes_, sizeof(unsigned long long)));
+  d_lk_bytes_ = DevBuf<unsigned long long>(1);
   HP_HIP(hipMemsetAsync(d_lk_bytes_, 0, sizeof(unsigned long long), s_));
-  HP_HIP(hipMalloc(&d_sort_stats_, sizeof(int)));
+  d_sort_stats_ = DevBuf<int>(1);
   HP_HIP(hipMemsetAsync(d_sort_stats_, 0, sizeof(int), s_));
 }
 
@@ -209,30 +210,7 @@ Tracker::~Tracker() {
     wcv_.notify_all();
     worker_.join();
   }
-  for (auto &kv : cs_) {
-    for (int k = 0; k < 2; k++)
-      if (kv.second.pyr_mem[k]) (void)hipFree(kv.second.pyr_mem[k]);
-    if (kv.second.d_raw) (void)hipFree(kv.second.d_raw);
-    if (kv.second.d_half) (void)hipFree(kv.second.d_half);
-    if (kv.second.d_hist) (void)hipFree(kv.second.d_hist);
-    if (kv.second.d_clahe_lut) (void)hipFree(kv.second.d_clahe_lut);
-    if (kv.second.d_score) (void)hipFree(kv.second.d_score);
-  }
-  if (d_lk_bytes_) (void)hipFree(d_lk_bytes_);
-  if (d_sort_stats_) (void)hipFree(d_sort_stats_);
-  if (ev_match_) (void)hipEventDestroy(ev_match_);
-  if (ev_up_) (void)hipEventDestroy(ev_up_);
-  if (up_) (void)hipStreamDestroy(up_);
-  if (ev_pyr_) (void)hipEventDestroy(ev_pyr_);
-  if (sd_) {
-    (void)hipStreamSynchronize(sd_);
-    (void)hipStreamDestroy(sd_);
-  }
-  if (b_) {
-    if (b_->dmem) (void)hipFree(b_->dmem);
-    if (b_->hmem) (void)hipHostFree(b_->hmem);
-    delete b_;
-  }
+  if (sd_) (void)hipStreamSynchronize(sd_);  // the detection stream's work ends before any member is released
 }
 
 // The tracker's device buffers an upload writes are read only by this frame's later launches: the previous
@@ -243,8 +221,8 @@ void Tracker::upload(void *dst, const void *src, size_t bytes) {
     return;
   }
   if (!up_) {
-    HP_HIP(hipStreamCreateWithFlags(&up_, hipStreamNonBlocking));
-    HP_HIP(hipEventCreateWithFlags(&ev_up_, hipEventDisableTiming));
+    up_ = Stream::create();
+    ev_up_ = Event::create();
   }
   if (hipStreamQuery(s_) == hipSuccess) {  // nothing to overlap: the cross-stream wait would only add latency
     HP_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s_));
@@ -271,15 +249,14 @@ void Tracker::sync() {
 void Tracker::ensure_cap(int n) {
   Bufs &b = *b_;
   if (n <= b.cap) return;
+  const int cap = std::max(n, 2 * b.cap);
   if (b.dmem) {
     if (sd_) spin_sync(sd_);
     if (cur_ != s_) spin_sync(s_);  // predetect: the frame's updates hold no tracker buffer, but wait anyway
     sync();
-    HP_HIP(hipFree(b.dmem));
-    HP_HIP(hipHostFree(b.hmem));
-    b.dmem = b.hmem = nullptr;
+    b.cap = 0;  // a throw below leaves the capacity that the empty handles have
+    b.dmem.reset(), b.hmem.reset();
   }
-  int cap = std::max(n, 2 * b.cap);
   size_t ncell = (size_t)b.maxcells * kMaxCams;  // the grid cells of every camera of one feed
   for (int pass = 0; pass < 2; pass++) {
     Arena d;
@@ -311,8 +288,8 @@ void Tracker::ensure_cap(int n) {
     b.spmask = d.take<float>(spmask_host_.size());
     if (pass == 0) {
       b.mirror = mirror;
-      HP_HIP(hipMalloc(&b.dmem, d.off + 256));
-      HP_HIP(hipHostMalloc(&b.hmem, mirror + 256, hipHostMallocDefault));
+      b.dmem = DevBuf<char>(d.off + 256);
+      b.hmem = PinBuf<char>(mirror + 256);
     }
   }
   b.cap = cap;
@@ -322,9 +299,9 @@ void Tracker::ensure_cap(int n) {
 Tracker::CamState &Tracker::cam_state(int cid) {
   auto it = cs_.find(cid);
   if (it != cs_.end()) return it->second;
-  CamState &c = cs_[cid];
+  CamState c;  // enters the map complete: a throw in alloc_pyr leaves no half-allocated camera behind
   alloc_pyr(c, cams_[cid].w, cams_[cid].h);
-  return c;
+  return cs_.emplace(cid, std::move(c)).first->second;
 }
 
 // buildOpticalFlowPyramid level sizes (stops once the next side would be <= win) for both slots
@@ -346,20 +323,20 @@ void Tracker::alloc_pyr(CamState &c, int w, int h) {
     if (lw <= win_ || lh <= win_) break;
   }
   for (int k = 0; k < 2; k++) {
-    HP_HIP(hipMalloc(&c.pyr_mem[k], bytes));
+    c.pyr_mem[k] = DevBuf<char>(bytes);
     c.pyr[k] = p;
     for (int l = 0; l < p.levels; l++) {
       c.pyr[k].img[l] = (const uint8_t *)((char *)c.pyr_mem[k] + img_off[l]);
       c.pyr[k].der[l] = (const int16_t *)((char *)c.pyr_mem[k] + der_off[l]);
     }
   }
-  HP_HIP(hipMalloc(&c.d_raw, (size_t)w * h * (downsample_ ? 4 : 1)));
-  if (downsample_) HP_HIP(hipMalloc(&c.d_half, (size_t)w * h));
-  HP_HIP(hipMalloc(&c.d_hist, 256 * sizeof(unsigned)));
+  c.d_raw = DevBuf<uint8_t>((size_t)w * h * (downsample_ ? 4 : 1));
+  if (downsample_) c.d_half = DevBuf<uint8_t>((size_t)w * h);
+  c.d_hist = DevBuf<unsigned>(256);
   HP_HIP(hipMemset(c.d_hist, 0, 256 * sizeof(unsigned)));  // cleared after use by each frame's pyramid
   // CLAHE: the 64 tile LUTs, rebuilt by every frame's k_clahe_lut before level 0 reads them
-  if (histogram_method_ == 2) HP_HIP(hipMalloc(&c.d_clahe_lut, kClaheLutBytes));
-  HP_HIP(hipMalloc(&c.d_score, (size_t)w * h));
+  if (histogram_method_ == 2) c.d_clahe_lut = DevBuf<uint8_t>(kClaheLutBytes);
+  c.d_score = DevBuf<uint8_t>((size_t)w * h);
 }
 
 // RANSACPointSetRegistrator::getSubset draws (ptsetreg.cpp), one rng per findFundamentalMat call
@@ -468,7 +445,7 @@ void Tracker::feed(double t, int ncam, const int *cam_ids, const uint8_t *const 
       KScope ks(kp_, KC_PYR);
       launch_pyramids(s_, job);
     }
-    if (!ev_pyr_) HP_HIP(hipEventCreateWithFlags(&ev_pyr_, hipEventDisableTiming));
+    if (!ev_pyr_) ev_pyr_ = Event::create();
     HP_HIP(hipEventRecord(ev_pyr_, s_));
     if (kp_) kp_->credit(KC_PYR, 0.0, pyramid_bytes(job));
   };
@@ -959,7 +936,7 @@ void Tracker::match_run(MatchJob *jobs, int nj) {
   HP_HIP(hipMemcpyAsync(b.hp(b.p1[lo]), b.p1[lo], span(b.p1[lo], b.p1n[hi] + 2 * b.cap), hipMemcpyDeviceToHost, s_));
   if (in_flight_) {
     // wait for the matching results only, not for the work the callback enqueues behind them
-    if (!ev_match_) HP_HIP(hipEventCreateWithFlags(&ev_match_, hipEventDisableTiming));
+    if (!ev_match_) ev_match_ = Event::create();
     HP_HIP(hipEventRecord(ev_match_, s_));
     std::function<void()> f = std::move(in_flight_);
     in_flight_ = nullptr;
@@ -1309,7 +1286,7 @@ void Tracker::worker_loop() {
 // The detection stream (created on first use).  Measured and dropped (gpurun_out/cum): restricting it to a CU subset
 // (hipExtStreamCreateWithCUMask, half / 7 of 8 / every other CU) left cfg3 within the run-to-run spread.
 void Tracker::make_detect_stream() {
-  if (!sd_) HP_HIP(hipStreamCreateWithFlags(&sd_, hipStreamNonBlocking));
+  if (!sd_) sd_ = Stream::create();
 }
 
 void Tracker::predetect_async() {

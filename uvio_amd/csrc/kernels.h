@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "dev_mem.h"
 #include "hp_math.h"
 #include "kprof.h"
 
@@ -158,13 +159,13 @@ void launch_feature_linearize(hipStream_t s, const DBatchParams &bp, const DFeat
 // batched chi2 gate (kernels_chi2.hip): T = H_all P[hidx, hidx], per-feature S / LDL^T / chi2;
 // rejected MSCKF / SLAM features get zero rows.  T_all: like H_all.
 // pcan: n^2 scratch for the gathered P_can of the tiled product (m >= 4096), or null
-// sbuf / sbuf_cap: the engine's buffer for the per-feature S of features too large for k_chi2's LDS staging
+// sbuf: the engine's buffer for the per-feature S of features too large for k_chi2's LDS staging
 // (formed by k_chi2_S2 / k_chi2_S over many CUs, grown here on demand)
 // small_gate: every feature is mode 1 and acc_count is already zero (launch_feature_linearize's zero): with
 // max_rows_f <= 16 the gate is the single launch k_chi2_small
 void launch_chi2_batch(hipStream_t s, const DBatchParams &bp, const DFeat *feats, const double *P, const int *hidx,
                        double *H_all, int m, double *T_all, const double *chi2_table, DFeatOut *out, int max_rows_f,
-                       int *acc_count, double *pcan, double **sbuf, size_t *sbuf_cap, bool small_gate);
+                       int *acc_count, double *pcan, DevBuf<double> &sbuf, bool small_gate);
 size_t feature_lds_bytes(int max_meas, int max_nf);
 
 // Compression: G = A^T A over rows of A = H_all (m x (n+1), ld = ldh), partials then Cholesky ->
@@ -389,6 +390,7 @@ void launch_fast_multi(hipStream_t s, const FastJob &job, const int *cells, int 
                        int *sort_stats = nullptr);
 // Test probe of the Grider_GRID.h:128 std::sort emulation: per cell (responses resp[off[c] .. off[c+1]) in raster
 // order) the arrangement after the introsort loop and, for kmax > 0, the top-min(n, kmax) raster indices in order
+constexpr int kSortStack = 64;  // entries of the introsort emulation's segment stack: the depth limit it can hold
 void launch_grid_order_probe(hipStream_t s, const uint8_t *resp, const int *off, int ncell, int nmax, int kmax,
                              int depth, int *arrangement, int *top);
 void launch_fast_cells(hipStream_t s, const uint8_t *img, int w, int h, const int *cells, int ncell, int sw, int sh, int thr,

@@ -579,7 +579,7 @@ static size_t chi2_small_lds_bytes(int n) {
 
 void launch_chi2_batch(hipStream_t s, const DBatchParams &bp, const DFeat *feats, const double *P, const int *hidx,
                        double *H_all, int m, double *T_all, const double *chi2_table, DFeatOut *out, int max_rows_f,
-                       int *acc_count, double *pcan, double **sbuf, size_t *sbuf_cap, bool small_gate) {
+                       int *acc_count, double *pcan, DevBuf<double> &sbuf, bool small_gate) {
   if (bp.nfeat <= 0 || m <= 0) return;
   const int n = bp.n_canon;
   if (small_gate && max_rows_f <= kGateMaxRows && !(slam_seven_parts() & kSevenGate)) {
@@ -628,20 +628,12 @@ void launch_chi2_batch(hipStream_t s, const DBatchParams &bp, const DFeat *feats
   if (!use_lds) {
     stride = (size_t)max_rows_f * (max_rows_f | 1);
     const size_t need = stride * (size_t)bp.nfeat;
-    if (need > *sbuf_cap) {
-      auto ok = [](hipError_t e, const char *what) {
-        if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-      };
-      if (*sbuf) {
-        ok(hipStreamSynchronize(s), "chi2 S buffer: stream sync");  // the old buffer may still be read
-        ok(hipFree(*sbuf), "chi2 S buffer: free");
-      }
-      *sbuf = nullptr;
-      *sbuf_cap = 0;
-      ok(hipMalloc(sbuf, need * 3 / 2 * sizeof(double)), "chi2 S buffer: alloc");
-      *sbuf_cap = need * 3 / 2;
+    if (need > sbuf.size()) {
+      if (sbuf) HP_HIP(hipStreamSynchronize(s));  // the old buffer may still be read
+      sbuf.reset();  // before the allocation: the peak stays one buffer, and a failed allocation leaves none
+      sbuf = DevBuf<double>(need * 3 / 2);
     }
-    Sg = *sbuf;
+    Sg = sbuf;
     const int nt = (max_rows_f + 15) / 16, groups = (nt * (nt + 1) / 2 + kChiSWaves - 1) / kChiSWaves;
     const size_t s2_bytes = (size_t)2 * 16 * nt * (kS2KC + 1) * sizeof(double);
     if (nt * (nt + 1) / 2 <= kS2Waves * kS2Tiles) {

@@ -765,7 +765,7 @@ __device__ void grid_introsort(int *arr, int n, int t, int depth, unsigned short
 // raster order (cv::FAST's), runs the introsort emulation above and writes the top kmax by (response desc,
 // arrangement position asc) -- Grider_GRID.h:128's std::sort order -- as (x, y, response) in image coordinates.
 // Strict NMS leaves no two adjacent survivors, so a cell has at most ceil(sw/2) ceil(sh/2) candidates.
-constexpr int kFastThreads = 1024, kFastMaxK = 64, kSortStack = 64;
+constexpr int kFastThreads = 1024, kFastMaxK = 64;  // (kSortStack: kernels.h)
 __host__ __device__ inline int fast_max_cand(int sw, int sh) { return ((sw + 1) / 2) * ((sh + 1) / 2); }
 __host__ __device__ inline size_t fast_lds_bytes(int sw, int sh) {
   return (size_t)fast_max_cand(sw, sh) * 8 + (((size_t)sw * sh + 15) & ~(size_t)15);

@@ -131,9 +131,7 @@ void Engine::shard_init_host(int rank, int world, uvio_hp_allreduce_fn fn, void 
   if (world < 1 || rank < 0 || rank >= world || !fn) throw HpError(UVIO_HP_E_ARG, "bad rank / world / callback");
   if (shard_.nccl) rccl_comm_destroy(shard_.nccl);
   shard_ = ShardComm{};
-  if (!d_.shard_host)
-    HP_HIP(hipHostMalloc((void **)&d_.shard_host, sizeof(double) * ((size_t)d_.max_ncol * d_.max_ncol + 2),
-                         hipHostMallocDefault));
+  if (!d_.shard_host) d_.shard_host = PinBuf<double>((size_t)d_.max_ncol * d_.max_ncol + 2);
   shard_.host_fn = fn;
   shard_.host_user = user;
   shard_.rank = rank;

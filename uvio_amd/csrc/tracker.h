@@ -9,6 +9,7 @@
 #include <condition_variable>
 #include <exception>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <unordered_map>
@@ -78,14 +79,14 @@ class Tracker {
  private:
   struct CamState {
     DPyr pyr[2]{};
-    void *pyr_mem[2] = {nullptr, nullptr};
+    DevBuf<char> pyr_mem[2];  // pyr[k]'s levels are views into pyr_mem[k]
     int last = 0;            // slot of pyr_last
     bool have_last = false;
-    uint8_t *d_raw = nullptr;  // staging of a host image (the raw 2w x 2h one with downsample_cameras)
-    uint8_t *d_half = nullptr;  // downsample_cameras: the pyrDown'ed input (w x h)
-    unsigned *d_hist = nullptr;
-    uint8_t *d_clahe_lut = nullptr;  // histogram_method 2: the 8 x 8 tile LUTs (kClaheLutBytes)
-    uint8_t *d_score = nullptr;  // FAST score map (w x h)
+    DevBuf<uint8_t> d_raw;   // staging of a host image (the raw 2w x 2h one with downsample_cameras)
+    DevBuf<uint8_t> d_half;  // downsample_cameras: the pyrDown'ed input (w x h)
+    DevBuf<unsigned> d_hist;
+    DevBuf<uint8_t> d_clahe_lut;  // histogram_method 2: the 8 x 8 tile LUTs (kClaheLutBytes)
+    DevBuf<uint8_t> d_score;  // FAST score map (w x h)
     std::vector<uint8_t> mask_last, mask_new;  // host masks (empty = none)
     std::vector<KeyPt> pts_last;
     std::vector<size_t> ids_last;
@@ -99,12 +100,17 @@ class Tracker {
   struct Bufs;
 
   const CamParams *cams_;
-  hipStream_t s_;
+  hipStream_t s_;  // the engine's stream (not owned)
+  // The tracker's own streams, declared before every buffer and event used on them: members die in reverse order,
+  // so the buffers and events go first.  up_: host-to-device uploads on their own stream (the DMA transfer overlaps
+  // the kernels queued before it, the pyramid, instead of starting after them; s_ waits on ev_up_ before its next
+  // launch).  sd_: the detection stream (predetect).  Both are created on first use.
+  Stream up_, sd_;
   KProf *kp_ = nullptr;
   KProf kp_pre_;  // the detection stream's event pairs (used by the worker thread while pre_mode_)
   KProf *kcur() { return pre_mode_ ? &kp_pre_ : kp_; }
-  unsigned long long *d_lk_bytes_ = nullptr;
-  int *d_sort_stats_ = nullptr;              // k_fast_select's count of introsort cells
+  DevBuf<unsigned long long> d_lk_bytes_;
+  DevBuf<int> d_sort_stats_;                 // k_fast_select's count of introsort cells
   unsigned long long grid_cells_ = 0;        // cells launched (host count, the feeding or the worker thread)
   bool downsample_ = false;  // VioManager.cpp:270-278: the inputs are 2w x 2h and pyrDown'ed first
   int num_features_, threshold_, grid_x_, grid_y_, min_px_dist_, histogram_method_;
@@ -112,16 +118,13 @@ class Tracker {
   const int pyr_levels_ = 5, win_ = 15;
   std::unordered_map<int, CamState> cs_;
   std::vector<float> spmask_host_;
-  Bufs *b_ = nullptr;
+  std::unique_ptr<Bufs> b_;  // (incomplete here: ~Tracker is defined in engine_track.cpp)
   std::unordered_map<int, std::vector<int>> subset_cache_;
   std::function<void()> in_flight_;
-  hipEvent_t ev_match_ = nullptr;
+  Event ev_match_;
   HostProf own_hp_;                // used when the engine does not share its own
   HostProf *hp_ = &own_hp_;        // the engine's section timer (UVIO_HP_HOST_PROF)
-  // host-to-device uploads on their own stream: the DMA transfer overlaps the kernels queued before it (the
-  // pyramid) instead of starting after them; s_ waits on ev_up_ before its next launch
-  hipStream_t up_ = nullptr;
-  hipEvent_t ev_up_ = nullptr;
+  Event ev_up_;
   void upload(void *dst, const void *src, size_t bytes);
   // the frame's decimation + pyramid launches, deferred until the new pyramid is first needed: the detection on
   // the previous frame's pyramid and the upload of the matching inputs go out before it, so the upload's DMA
@@ -140,9 +143,9 @@ class Tracker {
   void sync();
   void make_detect_stream();
   // detection stream state: the detection functions launch on cur_ (s_, or sd_ while predetect runs)
-  hipStream_t sd_ = nullptr, cur_ = nullptr;
+  hipStream_t cur_ = nullptr;  // an alias of s_ or sd_
   bool pre_pyr_waited_ = false;  // predetect_async enqueued sd_'s wait on ev_pyr_ (the worker must not read it)
-  hipEvent_t ev_pyr_ = nullptr;  // after the last pyramid launch on s_ (predetect reads that pyramid)
+  Event ev_pyr_;                 // after the last pyramid launch on s_ (predetect reads that pyramid)
   bool pre_mode_ = false;
   struct PreDet {
     bool valid = false;
