@@ -12,7 +12,8 @@
  *
  * Threading (mirrors the reference, SURVEY §8b "Threading"): uvio_hp_feed_imu may be
  * called concurrently with the other feeds (IMU buffer is mutex-guarded like
- * Propagator::imu_data_mtx, Propagator.h:68); camera / sim / UWB feeds must be
+ * Propagator::imu_data_mtx, Propagator.h:68), and so may uvio_hp_fast_state_propagate (it reads
+ * a snapshot published by the feed thread); camera / sim / UWB feeds and every other call must be
  * serialized by the caller (single update thread, ROS1Visualizer.h:173).
  *
  * No torch / Eigen / OpenCV types cross this boundary: plain pointers and sizes.
@@ -277,6 +278,42 @@ int uvio_hp_get_tracks(uvio_hp_t *h, int cam, uint64_t *ids, float *uv, int cap,
  * the (equalized) u8 image (w*h) and interleaved Scharr (dx, dy) int16 derivatives (w*h*2); img / der
  * may be NULL, cap = pixels available */
 int uvio_hp_get_pyramid(uvio_hp_t *h, int cam, int level, int *w, int *hgt, uint8_t *img, int16_t *der, size_t cap);
+/* StateHelper::get_marginal_covariance (StateHelper.cpp:226-254): block k is the variable with covariance id
+ * ids[k] and size sizes[k] (uvio_hp_get_state_vector's meta); out is m x m, m = sum sizes, leading dimension ld.
+ * The blocks may come in any order and may repeat (the reference copies whatever list it is given).  The rows
+ * and columns are gathered on the device into a dense block and only that block is copied back (the pose
+ * covariance of ROS1Visualizer.cpp:618, 805 is 36 numbers of an N x N matrix).  nvar == 0 does nothing.
+ * UVIO_HP_E_ARG: null pointers, nvar < 0, a size < 1, a block outside [0, N), ld < m; UVIO_HP_E_CAPACITY: m above
+ * the covariance capacity; every check comes before any device work, and a refused call leaves out untouched.
+ * Serialized with the feeds, like the other getters. */
+int uvio_hp_get_marginal_cov(uvio_hp_t *h, int nvar, const int *ids, const int *sizes, double *out, int ld);
+/* VioManager::get_good_features_MSCKF (VioManager.h:123, filled at VioManager.cpp:555-570): p_FinG (3 per feature)
+ * of the features the frame's MSCKF update kept, in the update's order (the status-0 entries of
+ * uvio_hp_debug_last_msckf).  As in the reference the list is cleared only by a frame whose first camera id is 0
+ * and appended to otherwise.  *n receives the number of features (E_CAPACITY if > cap). */
+int uvio_hp_get_good_features_msckf(uvio_hp_t *h, double *xyz_inG, int cap, int *n);
+/* switch the odometry cache on / off (off by default).  On: the calls after which the reference invalidates its
+ * cache (Propagator::invalidate_cache: VioManager.cpp:230, 303, 526, 543, UVioManager.cpp:161 -- a frame that ends
+ * in a zero-velocity update or reaches its update stage, uvio_hp_msckf_update, uvio_hp_slam_update) and the calls
+ * that set the state (uvio_hp_initialize_with_gt, a static initialization, uvio_hp_set_state, this call) publish
+ * the IMU state, its 15 x 15 marginal, calib_camimu_dt and the IMU intrinsics as the cache's next content: one
+ * 15 x 15 device gather and a 1.8 KB copy per such call, no host wait.  A frame that returns before its update
+ * stage, a propagation, a delayed initialization, uvio_hp_uwb_update_single and the marginalization calls leave the
+ * cache alone, as the reference does.  Serialized with the feeds. */
+int uvio_hp_odometry_enable(uvio_hp_t *h, int on);
+/* Propagator::fast_state_propagate (Propagator.cpp:140-267; ROS1Visualizer::visualize_odometry,
+ * ROS1Visualizer.cpp:245-327): state_plus = [q_GtoI(4) p_IinG(3) v_IinI(3) w_IinI(3)],
+ * cov 12 x 12 row-major in the reference's order (theta, p, v local, w); *ok = 0 where the reference returns false
+ * (fewer than two IMU readings for the interval: state_plus and cov are left untouched).  The cache is left at t
+ * with a zero time offset, so successive queries chain, as in the reference.
+ * Threading: may be called from any thread beside every other call on the handle (the IMU callback's thread,
+ * ROS1Visualizer.cpp:67).  A query that arrives while a frame is running uses the previous cache; the first query
+ * after the frame adopts the snapshot the frame published (the reference reads the live state inside that query
+ * instead, racing with the update thread).  The IMU intrinsics (Dw, Da, Tg, R_ACCtoIMU, R_GYROtoIMU) are taken with
+ * the snapshot, where the reference reads them live on every call: the two differ only after a state change that
+ * did not invalidate the cache.
+ * UVIO_HP_E_STATE: the cache is off, or the filter is not initialized.  The call does not set uvio_hp_last_error. */
+int uvio_hp_fast_state_propagate(uvio_hp_t *h, double t, double state_plus[13], double cov[144], int *ok);
 
 /* ---- Updater-level boundary: one updater call on the handle's current state ----
  * These mirror the reference's Updater C++ surfaces for a caller that keeps its own feature database

@@ -163,6 +163,49 @@ class Manager {
     check(uvio_hp_get_timing(h_, &t));
     return t;
   }
+  // StateHelper::get_marginal_covariance: blocks = (covariance id, size) per variable, any order, repeats allowed;
+  // row-major m x m, m = the sum of the sizes (the pose covariance of publish_state: {{imu id, 6}})
+  std::vector<double> marginal_covariance(const std::vector<std::pair<int, int>> &blocks) const {
+    std::vector<int> ids, sizes;
+    size_t m = 0;
+    for (const auto &b : blocks) {
+      ids.push_back(b.first);
+      sizes.push_back(b.second);
+      if (b.second > 0) m += (size_t)b.second;
+    }
+    std::vector<double> out(m * m);
+    check(uvio_hp_get_marginal_cov(h_, (int)blocks.size(), ids.data(), sizes.data(), out.data(), (int)m));
+    return out;
+  }
+  // VioManager::get_good_features_MSCKF: p_FinG, 3 per feature
+  std::vector<double> good_features_MSCKF() const {
+    int n = 0;
+    const int rc = uvio_hp_get_good_features_msckf(h_, nullptr, 0, &n);
+    if (rc != UVIO_HP_E_CAPACITY) check(rc);
+    std::vector<double> p((size_t)3 * n);
+    if (n > 0) check(uvio_hp_get_good_features_msckf(h_, p.data(), n, &n));
+    return p;
+  }
+
+  // ---- IMU-rate odometry (Propagator::fast_state_propagate, ROS1Visualizer::visualize_odometry) ----
+  struct Odometry {
+    std::array<double, 13> state_plus{};   // q_GtoI(4) p_IinG(3) v_IinI(3) w_IinI(3)
+    std::array<double, 144> covariance{};  // row-major 12 x 12: theta, p, v (local), w
+  };
+  void enable_odometry(bool on = true) { check(uvio_hp_odometry_enable(h_, on ? 1 : 0)); }
+  // false where the reference returns false, and before initialization or with the cache off, where
+  // visualize_odometry returns without publishing (ROS1Visualizer.cpp:247-256); out is then untouched.  Callable
+  // from any thread beside every other call on the manager (the IMU callback); an error carries the code only
+  // (the message belongs to the feed thread).
+  bool fast_state_propagate(double t, Odometry &out) const {
+    int ok = 0;
+    Odometry o;
+    const int rc = uvio_hp_fast_state_propagate(h_, t, o.state_plus.data(), o.covariance.data(), &ok);
+    if (rc == UVIO_HP_E_STATE) return false;
+    if (rc) throw Error(rc, "uvio_hp_fast_state_propagate");
+    if (ok) out = o;
+    return ok != 0;
+  }
 
   // ---- updater-level calls (uvio_hp.h "Updater-level boundary") ----
   void set_state(const std::vector<double> &val, const std::vector<double> &fej, const std::vector<double> &P) {
@@ -231,6 +274,18 @@ class Manager {
     return out;
   }
 };
+
+// nav_msgs::Odometry's two 6 x 6 covariances from fast_state_propagate's 12 x 12 (ROS1Visualizer.cpp:311-325):
+// ROS orders a pose as position, then orientation, so the (theta, p) blocks swap; the twist (v local, w) is kept
+inline void odometry_covariance_ros(const std::array<double, 144> &cov, std::array<double, 36> &pose,
+                                    std::array<double, 36> &twist) {
+  static const int perm[12] = {3, 4, 5, 0, 1, 2, 6, 7, 8, 9, 10, 11};
+  for (int r = 0; r < 6; r++)
+    for (int c = 0; c < 6; c++) {
+      pose[(size_t)(6 * r + c)] = cov[(size_t)(12 * perm[r] + perm[c])];
+      twist[(size_t)(6 * r + c)] = cov[(size_t)(12 * perm[r + 6] + perm[c + 6])];
+    }
+}
 
 // histogram_method CLAHE (cv::createCLAHE(10.0, Size(8, 8))->apply) of one 8-bit image with the tracker's own
 // kernels (uvio_hp_debug_clahe): w x h pixels, rows `stride` bytes apart, both sides >= 9; returns w * h packed

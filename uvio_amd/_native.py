@@ -155,6 +155,10 @@ SIGNATURES = [
     ("debug_grid_order", _I, [_P(C.c_uint8), _P(_I), _I, _I, _I, _P(_I), _P(_I)]),
     ("debug_clahe", _I, [_P(C.c_uint8), _I, _I, _I, _P(C.c_uint8)]),
     ("debug_grid_stats", _I, [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64)]),
+    ("get_marginal_cov", _I, [C.c_void_p, _I, _P(_I), _P(_I), _P(_D), _I]),
+    ("get_good_features_msckf", _I, [C.c_void_p, _P(_D), _I, _P(_I)]),
+    ("odometry_enable", _I, [C.c_void_p, _I]),
+    ("fast_state_propagate", _I, [C.c_void_p, _D, _P(_D), _P(_D), _P(_I)]),
 ]
 
 # uvio_hp_allreduce_fn: int (*)(double *buf, size_t count, void *user)

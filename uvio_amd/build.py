@@ -25,6 +25,7 @@ SOURCES = [
     "engine_track.cpp",
     "engine_retri.cpp",
     "engine_api.cpp",
+    "engine_odom.cpp",
     "capi.cpp",
     "shard.cpp",
     "kernels_cov.hip",

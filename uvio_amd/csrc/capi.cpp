@@ -252,6 +252,35 @@ int uvio_hp_get_clone_times(uvio_hp_t *h, double *out, int cap, int *n) {
   return 0;
 }
 
+int uvio_hp_get_marginal_cov(uvio_hp_t *h, int nvar, const int *ids, const int *sizes, double *out, int ld) {
+  if (!h) return UVIO_HP_E_ARG;
+  HP_GUARD(h, return h->e->marginal_cov(nvar, ids, sizes, out, ld);)
+}
+
+int uvio_hp_get_good_features_msckf(uvio_hp_t *h, double *xyz_inG, int cap, int *n) {
+  if (!h || !n || cap < 0 || (cap > 0 && !xyz_inG)) return UVIO_HP_E_ARG;
+  *n = h->e->good_features_msckf(xyz_inG, cap);
+  return *n <= cap ? 0 : UVIO_HP_E_CAPACITY;
+}
+
+int uvio_hp_odometry_enable(uvio_hp_t *h, int on) {
+  if (!h) return UVIO_HP_E_ARG;
+  HP_GUARD(h, h->e->odometry_enable(on != 0); return 0;)
+}
+
+// Runs beside every other call on the handle: it does not touch the handle's error message (the feed thread's)
+int uvio_hp_fast_state_propagate(uvio_hp_t *h, double t, double state_plus[13], double cov[144], int *ok) {
+  if (!h || !state_plus || !cov || !ok) return UVIO_HP_E_ARG;
+  try {
+    HP_HIP(hipSetDevice(h->e->device()));
+    return h->e->fast_state_propagate(t, state_plus, cov, ok);
+  } catch (const HpError &ex) {
+    return ex.code;
+  } catch (const std::exception &) {
+    return UVIO_HP_E_INTERNAL;
+  }
+}
+
 // ---- Updater-level boundary (include/uvio_hp.h) ----
 int uvio_hp_set_state(uvio_hp_t *h, const double *val, const double *fej, int len, const double *P, int N, int ld) {
   if (!h || !val || !fej || !P || len <= 0 || N <= 0) return UVIO_HP_E_ARG;

@@ -20,7 +20,9 @@
 #include <vector>
 
 #include "hp_common.h"
+#include "fast_prop.h"
 #include "hprof.h"
+#include "imu_math.h"
 #include "kernels.h"
 #include "pool.h"
 #include "tracker.h"
@@ -317,10 +319,6 @@ void *rccl_comm_init(int rank, int world, const uint8_t id[128]);
 void rccl_allreduce_sum(void *comm, double *buf, size_t count, hipStream_t s);
 void rccl_comm_destroy(void *comm);
 
-struct ImuSample {
-  double t, wm[3], am[3];
-};
-
 // Device-resident buffers (allocated once at create, sized from the config).  The handles own their memory;
 // the raw pointers beside them are views into `chain` / `chain_host` or into the EKF scratch arrays.
 struct DeviceBufs {
@@ -397,6 +395,17 @@ struct DeviceBufs {
   DevBuf<double> uwb_reg, uwb_h;
   PinBuf<double> uwb_host;
   size_t uwb_stride = 0;
+  // Engine::marginal_cov: the gathered m x m block and its pinned mirror (both grow on demand)
+  DevBuf<double> marg;
+  PinBuf<double> marg_host;
+  // IMU-rate odometry (engine_odom.cpp): the 15 x 15 IMU marginal of a published snapshot is gathered into one of
+  // two device slots and copied to the matching pinned slot behind the frame's last P write; the slot's event
+  // tells a query that its copy has landed.  odom_idx: the IMU's 15 covariance indices.
+  static constexpr int kOdomSlot = 15 * 15;
+  DevBuf<int> odom_idx;
+  DevBuf<double> odom_dev;
+  PinBuf<double> odom_host;
+  Event ev_odom[2];
 };
 
 // the per-feature measurement / variable tables of one feature in the reference iteration order (engine_update.cpp)
@@ -586,8 +595,38 @@ class Engine {
   // the reference routine the host was in when the last call failed (error messages)
   const char *stage() const { return stage_; }
 
+  // ---- marginal covariances, the MSCKF features of the frame, IMU-rate odometry (engine_odom.cpp) ----
+  // StateHelper::get_marginal_covariance (StateHelper.cpp:226-254): the blocks' rows and columns of P as one dense
+  // m x m matrix, gathered on the device
+  int marginal_cov(int nvar, const int *ids, const int *sizes, double *out, int ld);
+  // VioManager::get_good_features_MSCKF (VioManager.h:123): returns their number (the first cap are written)
+  int good_features_msckf(double *xyz_inG, int cap) const;
+  void odometry_enable(bool on);
+  // Propagator::fast_state_propagate (Propagator.cpp:140-267) from the odometry cache; any thread
+  int fast_state_propagate(double t, double *state_plus, double *cov, int *ok);
+
  private:
   const char *stage_ = "";
+  std::vector<double> good_feats_;  // good_features_MSCKF (VioManager.cpp:555-570), 3 per feature
+  // The odometry cache.  The feed thread marks it stale where the reference calls invalidate_cache()
+  // (odom_invalidate) and publishes a snapshot of the filter state at the end of that call (odom_flush); a query
+  // adopts the published snapshot before it integrates.  odom_mtx_ guards the cache and the published snapshot;
+  // odom_dirty_ and odom_slot_ belong to the feed thread.
+  struct OdomSnap {
+    bool pending = false;
+    int slot = 0;
+    double t = 0, t_off = 0, est[16] = {0};
+    fastprop::Calib calib{};
+  };
+  std::atomic<bool> odom_on_{false};
+  bool odom_dirty_ = false;
+  int odom_slot_ = 0;
+  std::mutex odom_mtx_;
+  OdomSnap odom_pub_;
+  fastprop::Cache odom_cache_;
+  bool odom_cache_valid_ = false;
+  void odom_invalidate() { odom_dirty_ = true; }
+  void odom_flush();
 
  private:
 
@@ -660,7 +699,6 @@ class Engine {
 
   // propagator (host mean + Phi/Qd, device covariance)
   std::vector<ImuSample> select_imu_readings(double t0, double t1);
-  static std::vector<ImuSample> select_imu(const std::vector<ImuSample> &imu, double t0, double t1);
   void accumulate_phi(const std::vector<ImuSample> &prop, std::vector<double> &Phi, std::vector<double> &Qd, int n);
   void predict_and_compute(const ImuSample &a, const ImuSample &b, double *F, double *Qd, int n);
   void last_w(const std::vector<ImuSample> &prop, double *w);

@@ -47,6 +47,8 @@ int Engine::api_set_state(const double *val, const double *fej, int len, const d
                           hipMemcpyHostToDevice, d_.stream));
   ++p_epoch_;
   dev_sync();
+  odom_invalidate();
+  odom_flush();
   return 0;
 }
 
@@ -83,6 +85,10 @@ int Engine::api_update(int which, int nfeat, const uint64_t *featids, const int 
     throw HpError(ex.code, std::string(routine[which]) + ": " + ex.what());
   }
   if (rc) return rc;
+  if (which != API_DELAYED) {  // VioManager.cpp:526, 543: after UpdaterMSCKF::update and UpdaterSLAM::update
+    odom_invalidate();
+    odom_flush();
+  }
   const std::vector<FeatDebug> &res = (which == API_MSCKF) ? last_msckf_ : last_upd_;
   std::unordered_map<size_t, const FeatDebug *> by_id;
   for (auto &d : res) by_id[d.id] = &d;

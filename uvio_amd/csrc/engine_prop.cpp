@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "engine.h"
+#include "imu_math.h"
 
 namespace uvhp {
 
@@ -71,45 +72,12 @@ void M3s(double s, const double *A, double *C) {
 void M3add(const double *A, const double *B, double *C) {
   for (int i = 0; i < 9; i++) C[i] = A[i] + B[i];
 }
-void eye3(double *I) {
-  for (int i = 0; i < 9; i++) I[i] = (i % 4 == 0) ? 1.0 : 0.0;
-}
 // 3 x nc = A(3x3) * B(3 x nc)
 void M3xN(const double *A, const double *B, int nc, double *C) {
   for (int i = 0; i < 3; i++)
     for (int j = 0; j < nc; j++) C[nc * i + j] = A[3 * i] * B[j] + A[3 * i + 1] * B[nc + j] + A[3 * i + 2] * B[2 * nc + j];
 }
 
-void exp_so3(const double *w, double *R) {
-  double th = norm3(w), A, B;
-  if (th < 1e-7) {
-    A = 1;
-    B = 0.5;
-  } else {
-    A = sin(th) / th;
-    B = (1 - cos(th)) / (th * th);
-  }
-  if (th == 0) {
-    eye3(R);
-    return;
-  }
-  double S[9], S2[9];
-  skew(w, S);
-  M3(S, S, S2);
-  for (int i = 0; i < 9; i++) R[i] = ((i % 4 == 0) ? 1.0 : 0.0) + A * S[i] + B * S2[i];
-}
-void Jl_so3(const double *w, double *J) {
-  double th = norm3(w);
-  if (th < 1e-6) {
-    eye3(J);
-    return;
-  }
-  double a[3] = {w[0] / th, w[1] / th, w[2] / th}, S[9];
-  skew(a, S);
-  double c1 = sin(th) / th, c2 = 1 - sin(th) / th, c3 = (1 - cos(th)) / th;
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) J[3 * i + j] = ((i == j) ? c1 : 0.0) + c2 * a[i] * a[j] + c3 * S[3 * i + j];
-}
 void log_so3(const double *R, double *w) {
   double R11 = R[0], R12 = R[1], R13 = R[2], R21 = R[3], R22 = R[4], R23 = R[5], R31 = R[6], R32 = R[7], R33 = R[8];
   double tr = R11 + R22 + R33;
@@ -136,24 +104,6 @@ void log_so3(const double *R, double *w) {
   }
 }
 
-// State::Dm / State::Tg (State.h:92-111)
-void Dm(int model, const double *v, double *D) {
-  for (int i = 0; i < 9; i++) D[i] = 0;
-  if (model == 0) {
-    D[0] = v[0];
-    D[3] = v[1]; D[4] = v[3];
-    D[6] = v[2]; D[7] = v[4]; D[8] = v[5];
-  } else {
-    D[0] = v[0]; D[1] = v[1]; D[2] = v[3];
-    D[4] = v[2]; D[5] = v[4];
-    D[8] = v[5];
-  }
-}
-void TgM(const double *v, double *T) {
-  T[0] = v[0]; T[1] = v[3]; T[2] = v[6];
-  T[3] = v[1]; T[4] = v[4]; T[5] = v[7];
-  T[6] = v[2]; T[7] = v[5]; T[8] = v[8];
-}
 // compute_H_Dw / compute_H_Da (3x6), compute_H_Tg (3x9)
 void H_D(int model, const double *w, double *H) {
   for (int i = 0; i < 18; i++) H[i] = 0;
@@ -179,52 +129,7 @@ std::vector<ImuSample> Engine::select_imu_readings(double time0, double time1) {
     std::lock_guard<std::mutex> lk(imu_mtx_);
     imu = imu_data_;
   }
-  return select_imu(imu, time0, time1);
-}
-
-// Propagator::select_imu_readings (Propagator.cpp:269-393) on a given buffer
-std::vector<ImuSample> Engine::select_imu(const std::vector<ImuSample> &imu, double time0, double time1) {
-  auto interp = [](const ImuSample &a, const ImuSample &b, double t) {
-    double lambda = (t - a.t) / (b.t - a.t);
-    ImuSample d;
-    d.t = t;
-    for (int k = 0; k < 3; k++) {
-      d.am[k] = (1 - lambda) * a.am[k] + lambda * b.am[k];
-      d.wm[k] = (1 - lambda) * a.wm[k] + lambda * b.wm[k];
-    }
-    return d;
-  };
-  std::vector<ImuSample> prop;
-  if (imu.empty()) return prop;
-  for (size_t i = 0; i < imu.size() - 1; i++) {
-    if (imu[i + 1].t > time0 && imu[i].t < time0) {
-      prop.push_back(interp(imu[i], imu[i + 1], time0));
-      continue;
-    }
-    if (imu[i].t >= time0 && imu[i + 1].t <= time1) {
-      prop.push_back(imu[i]);
-      continue;
-    }
-    if (imu[i + 1].t > time1) {
-      if (imu[i].t > time1 && i == 0) {
-        break;
-      } else if (imu[i].t > time1) {
-        prop.push_back(interp(imu[i - 1], imu[i], time1));
-      } else {
-        prop.push_back(imu[i]);
-      }
-      if (prop.back().t != time1) prop.push_back(interp(imu[i], imu[i + 1], time1));
-      break;
-    }
-  }
-  if (prop.empty()) return prop;
-  if (prop.back().t != time1) prop.push_back(interp(imu[imu.size() - 2], imu[imu.size() - 1], time1));
-  for (size_t i = 0; i + 1 < prop.size(); i++)
-    if (std::abs(prop[i + 1].t - prop[i].t) < 1e-12) {
-      prop.erase(prop.begin() + i);
-      i--;
-    }
-  return prop;
+  return select_imu(imu, time0, time1);  // imu_math.h
 }
 
 void Engine::predict_and_compute(const ImuSample &dm, const ImuSample &dp, double *Fout, double *Qdout, int n) {

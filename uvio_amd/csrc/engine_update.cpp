@@ -73,8 +73,12 @@ void Engine::initialize_with_gt(const double x[17]) {
   startup_time_ = x[0];
   is_initialized_ = true;
   db_cleanup_measurements(timestamp_);
-  std::lock_guard<std::mutex> lk(imu_mtx_);
-  init_imu_.clear();
+  {
+    std::lock_guard<std::mutex> lk(imu_mtx_);
+    init_imu_.clear();
+  }
+  odom_invalidate();
+  odom_flush();
 }
 
 // VioManager.cpp:166-189 + Propagator::feed_imu (Propagator.h:65-91)
@@ -392,6 +396,7 @@ int Engine::after_tracking(double t, const std::vector<int> &camids, clk::time_p
       return UVIO_HP_E_STATE;
     }
     is_initialized_ = true;
+    odom_invalidate();  // the odometry cache starts from the initializer's state, published at this frame's end
   }
   // zero-velocity update (UVioManager.cpp:147-162, VioManager.cpp:291-307): on success the frame ends here
   if (was_initialized && o_.try_zupt && (!o_.zupt_only_at_beginning || !has_moved_since_zupt_)) {
@@ -410,6 +415,8 @@ int Engine::after_tracking(double t, const std::vector<int> &camids, clk::time_p
       timing_.n_clones = (int)clones_.size();
       timing_.cov_dim = N_;
       timing_.total = secs(rT1, clk::now());
+      odom_invalidate();  // VioManager.cpp:230, 303, UVioManager.cpp:161
+      odom_flush();
       return 0;
     }
   }
@@ -435,6 +442,7 @@ int Engine::after_tracking(double t, const std::vector<int> &camids, clk::time_p
     past_uwb_.erase(past_uwb_.begin(), past_uwb_.upper_bound(t));
   }
   int rc = do_feature_propagate_update(t, camids, rT2);
+  if (rc == 0) odom_flush();  // the frame's snapshot for the IMU-rate odometry, if its update stage ran
   timing_.total = secs(rT1, clk::now());
   // VioManager.cpp:631-644: one row per frame that ran the whole update, times in the reference's columns
   // (the UWB ranges processed before the propagation land in "propagation", as in UVioManager.cpp:147-188)
@@ -643,9 +651,14 @@ int Engine::do_feature_propagate_update(double t, const std::vector<int> &camids
   // of max_slam_in_update (VioManager.cpp:533-545).  The chain also carries the feature-sharded MSCKF update:
   // over RCCL its all-reduce is enqueued; the host all-reduce (a callback, for ranks that share a GPU) waits for
   // this rank's Gram in the middle of the enqueueing
+  odom_invalidate();  // VioManager.cpp:526, 543
   rc = update_frame(up, slam_upd, slam_delayed, (size_t)std::max(o_.max_slam_in_update, 1));
   chain_overlap_ = nullptr;
   if (rc) return rc;
+  // VioManager.cpp:555-570: the features the MSCKF update kept, cleared on the base camera's frames only
+  if (camids.at(0) == 0) good_feats_.clear();
+  for (const auto &d : last_msckf_)
+    if (d.status == 0) good_feats_.insert(good_feats_.end(), d.p_FinG, d.p_FinG + 3);
   const auto rT6 = clk::now();
   timing_.msckf_update = chain_times_[0];
   timing_.slam_update = chain_times_[1];

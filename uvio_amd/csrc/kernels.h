@@ -149,6 +149,9 @@ void launch_compact(hipStream_t s, const double *P, double *Pout, int ld, int Nn
 void launch_marginalize_multi(hipStream_t s, const double *P, double *Pout, int ld, int Nn, const int *src);
 // diagonal check: writes count of negative diagonal entries to *neg (device int)
 void launch_check_diag(hipStream_t s, const double *P, int ld, int N, int *neg);
+// StateHelper::get_marginal_covariance (StateHelper.cpp:226-254): out (dense m x m) <- P[idx, idx] for m
+// covariance indices idx (device, any order, repeats allowed, each in [0, N) of P)
+void launch_marginal_gather(hipStream_t s, const double *P, int ld, const int *idx, int m, double *out);
 
 // MSCKF / SLAM per-feature linearization: triangulation (+LM), Jacobian, nullspace, chi2, rows to H_all
 // zero (optional): set to 0 (the accepted-feature count of the batch's gate, which k_chi2_small only adds to)

@@ -288,6 +288,19 @@ void launch_check_diag(hipStream_t s, const double *P, int ld, int N, int *neg) 
   hipLaunchKernelGGL(k_check_diag, dim3((N + 255) / 256), dim3(256), 0, s, P, ld, N, neg);
 }
 
+// out[i * m + j] = P[idx[i] * ld + idx[j]].  A 64 x 4 workgroup: the 64 lanes of a wave run along j, so the
+// contiguous columns of one variable are one coalesced load and the row of out one coalesced store.
+__global__ void k_marginal_gather(const double *__restrict__ P, int ld, const int *__restrict__ idx, int m,
+                                  double *__restrict__ out) {
+  const int j = blockIdx.x * 64 + threadIdx.x, i = blockIdx.y * 4 + threadIdx.y;
+  if (i >= m || j >= m) return;
+  out[(size_t)i * m + j] = P[(size_t)idx[i] * ld + idx[j]];
+}
+void launch_marginal_gather(hipStream_t s, const double *P, int ld, const int *idx, int m, double *out) {
+  if (m <= 0) return;
+  hipLaunchKernelGGL(k_marginal_gather, dim3((m + 63) / 64, (m + 3) / 4), dim3(64, 4), 0, s, P, ld, idx, m, out);
+}
+
 // ----------------------------------------------------------------------------------------------
 // Compression: Gram partials.  Grid: (upper tile pairs, row chunks).  Tile 32x32, 256 threads,
 // each thread 2x2 outputs.  A is m x ncol, row-major, ld = ldh.

@@ -458,6 +458,44 @@ class VioManager:
         self._check(self._call("get_clone_times", self._h, _dp(out), 256, C.byref(n)), "get_clone_times")
         return out[:n.value].copy()
 
+    # ---- what the ROS node reads after every message (ROS1Visualizer.cpp:245-327, 618, 687, 805) ----
+    def get_marginal_cov(self, blocks, ld=None):
+        """StateHelper::get_marginal_covariance: blocks = [(covariance id, size), ...] (get_state_vector's meta
+        columns 1 and 2), in any order, repeats allowed -> the (m, m) marginal, gathered on the device.  ld: the
+        leading dimension handed to the library (default m)."""
+        ids = np.ascontiguousarray([b[0] for b in blocks], dtype=np.int32)
+        sizes = np.ascontiguousarray([b[1] for b in blocks], dtype=np.int32)
+        m = int(sizes.sum()) if len(blocks) else 0
+        ld = m if ld is None else int(ld)
+        out = np.zeros((m, max(ld, 1)))
+        ip = C.POINTER(C.c_int)
+        self._check(self._call("get_marginal_cov", self._h, len(blocks), ids.ctypes.data_as(ip), sizes.ctypes.data_as(ip),
+                               _dp(out), ld), "get_marginal_cov")
+        return out[:, :m].copy()
+
+    def get_good_features_msckf(self):
+        """VioManager::get_good_features_MSCKF: (n, 3) p_FinG of the features the last MSCKF updates kept."""
+        n = C.c_int()
+        cap = 8192
+        out = np.zeros((cap, 3))
+        self._check(self._call("get_good_features_msckf", self._h, _dp(out), cap, C.byref(n)), "get_good_features_msckf")
+        return out[:n.value].copy()
+
+    def enable_odometry(self, on=True):
+        """Switch the IMU-rate odometry cache on / off (off by default)."""
+        self._check(self._call("odometry_enable", self._h, 1 if on else 0), "odometry_enable")
+
+    def fast_state_propagate(self, t):
+        """Propagator::fast_state_propagate: (state_plus (13,), cov (12, 12)) at IMU time t, or None where the
+        reference returns false.  May be called from another thread beside the feeds."""
+        sp = np.zeros(13)
+        cov = np.zeros((12, 12))
+        ok = C.c_int(0)
+        rc = self._call("fast_state_propagate", self._h, C.c_double(t), _dp(sp), _dp(cov), C.byref(ok))
+        if rc != 0:  # (the call leaves the handle's error message alone)
+            raise RuntimeError("fast_state_propagate failed: %s" % N.ERRNAMES.get(rc, rc))
+        return (sp, cov) if ok.value else None
+
 
 def ekf_update(P, H_index, H, res, sigma2, compressed=False):
     """StateHelper::EKFUpdate on a standalone covariance, on the device (returns P_new, dx).
