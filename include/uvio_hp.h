@@ -315,6 +315,43 @@ int uvio_hp_odometry_enable(uvio_hp_t *h, int on);
  * UVIO_HP_E_STATE: the cache is off, or the filter is not initialized.  The call does not set uvio_hp_last_error. */
 int uvio_hp_fast_state_propagate(uvio_hp_t *h, double t, double state_plus[13], double cov[144], int *ok);
 
+/* ---- image products ("Image products") ---- */
+/* VioManager::get_historical_viz_image (VioManagerHelper.cpp:389-415): the canvas of TrackBase::display_history
+ * (TrackBase.cpp:119-228) called with the colours (255, 255, 0) / (255, 255, 255) and the SLAM landmarks of the state
+ * as the highlighted ids, rendered on the device over level 0 of the last pyramids.  The canvas is 3-channel 8-bit,
+ * packed, row-major, *height x *width pixels: max_h x (ncam * max_w) over the cameras of the last camera feed in
+ * ascending camera id, camera k at x offset k * max_w.  Before the first camera feed *width = *height = 0 (the
+ * reference returns an empty cv::Mat) and nothing is written.  out == NULL only reports the size; otherwise cap is
+ * the bytes available (UVIO_HP_E_CAPACITY if fewer than 3 * *width * *height, with the size reported).
+ * *overlay names the text the reference would put on each camera's image: 0 = "CAM:k", 1 = "init" (not
+ * initialized), 2 = "zvupt" (the last frame ended in a zero-velocity update).  The glyphs themselves are NOT drawn:
+ * cv::putText needs OpenCV's Hershey font tables, which this library does not carry; an adapter that has OpenCV adds
+ * the text with one cv::putText per camera (position, scale and colour: TrackBase.cpp:213-219).  The image is always
+ * built from scratch (the reference's "draw on top of the previous image" branch is not reproduced); the drawing
+ * rules are listed in DESIGN.md.  Nothing is kept, copied or enqueued per frame for this call: it costs the feeds
+ * nothing unless it is made.  Serialized with the feeds, like the other getters. */
+int uvio_hp_get_track_image(uvio_hp_t *h, uint8_t *out, size_t cap, int *width, int *height, int *overlay);
+/* the same with out in device memory (a torch tensor, a GPU encoder's input): the call returns with the image
+ * complete */
+int uvio_hp_get_track_image_device(uvio_hp_t *h, uint8_t *out, size_t cap, int *width, int *height, int *overlay);
+/* Feature::uvs[cam] of feature id as the handle's database holds it, oldest first ((u, v) pairs, the first cap
+ * of them written; UVIO_HP_E_CAPACITY if *n > cap), how many cameras have seen the feature (Feature::uvs.size(),
+ * display_history's is_stereo test) and Feature::to_delete.  *n = 0 (and *n_cams = 0) when the feature is unknown.
+ * n_cams / to_delete may be NULL.  This is what an adapter needs to draw the tracks in a style of its own. */
+int uvio_hp_get_track_history(uvio_hp_t *h, int cam, uint64_t id, float *uv, int cap, int *n, int *n_cams,
+                              int *to_delete);
+/* The two images of ROS1Visualizer::publish_loopclosure_information (ROS1Visualizer.cpp:950-996) for camera 0, both
+ * *height x *width (camera 0's size): depth, the 16-bit map, zero except at ((int)v, (int)u) of every active track
+ * (uvio_hp_get_active_tracks, uvd_valid 1) whose (u, v) passes the function's border test (dw = 4), where it holds
+ * (uint16_t)(1000 * depth) (the low 16 bits of the truncated integer); viz (3 channels, packed), camera 0's last
+ * image (pyramid level 0) with the filled square of half-side dw per such track in the function's inverse-depth
+ * colour ramp.  The tracks are drawn in ascending feature id (the reference iterates an unordered_map: its order,
+ * and so which of two overlapping squares wins, is unspecified there).  Either pointer may be NULL; cap = pixels
+ * available in each given buffer (depth: cap uint16_t, viz: 3 * cap bytes; UVIO_HP_E_CAPACITY otherwise, with the
+ * size reported).  *t receives active_tracks_time (-1, with a zero size, before the first retriangulation or camera
+ * feed). */
+int uvio_hp_get_loop_depth(uvio_hp_t *h, uint16_t *depth, uint8_t *viz, size_t cap, int *width, int *height, double *t);
+
 /* ---- Updater-level boundary: one updater call on the handle's current state ----
  * These mirror the reference's Updater C++ surfaces for a caller that keeps its own feature database
  * (the feeds above run the whole VioManager frame instead).  Features come as flat arrays: feature i has
@@ -447,6 +484,40 @@ int uvio_hp_debug_grid_order(const uint8_t *resp, const int *off, int ncell, int
  * kernels on a one-level pyramid; out (w * h, packed) receives level 0.  UVIO_HP_E_ARG: null pointers, stride < w,
  * a side below 9; UVIO_HP_E_CAPACITY: a side above 16384. */
 int uvio_hp_debug_clahe(const uint8_t *img, int w, int h, int stride, uint8_t *out);
+/* One track of uvio_hp_debug_draw_tracks: what display_history reads of it.  (u, v): the track's point in
+ * pts_last (centre of the highlight box); hist_n (u, v) pairs from pair hist_off of the call's flat uv array: the
+ * feature's uvs of this camera, oldest first (hist_n = 0: the feature is unknown or has no measurement here). */
+typedef struct {
+  uint64_t id;
+  float u, v;
+  int highlighted; /* the id is in display_history's highlighted list */
+  int n_cams;      /* Feature::uvs.size() (> 1: the stereo colours) */
+  int to_delete;   /* Feature::to_delete */
+  int hist_off, hist_n;
+} uvio_hp_viz_track_t;
+/* uvio_hp_get_track_image's renderer on caller-given inputs (the very kernels the getter runs): ncam 8-bit images
+ * (imgs[k]: w[k] x h[k], rows strides[k] bytes apart), optional masks (masks == NULL or masks[k] == NULL: none;
+ * same size and stride as the image; set where > 127), and per camera counts[k] tracks, concatenated in tracks, in
+ * draw order, whose histories lie in uv (n_uv pairs).  out (cap bytes) receives the canvas as
+ * uvio_hp_get_track_image returns it; out == NULL only reports the size.  stage_ms (optional, 5 doubles): device
+ * milliseconds of the uploads, the base, primitive and compose kernels and the copy out (HIP events).
+ * UVIO_HP_E_ARG: null pointers, ncam outside 1..UVIO_HP_MAX_CAMS, a side < 1, stride < w, a negative count, a
+ * history outside uv; UVIO_HP_E_CAPACITY: out too small, a side above 16384, or more than 2^31 - 1 primitive
+ * pixels. */
+int uvio_hp_debug_draw_tracks(int ncam, const uint8_t *const *imgs, const int *w, const int *h, const int *strides,
+                              const uint8_t *const *masks, const int *counts, const uvio_hp_viz_track_t *tracks,
+                              const float *uv, int n_uv, uint8_t *out, size_t cap, int *width, int *height,
+                              double *stage_ms);
+/* uvio_hp_get_loop_depth's two images on caller-given inputs through the same path: an 8-bit w x h image (rows
+ * stride bytes apart) and n tracks (ids[i], uvd[3 i .. 3 i + 2] = u, v, depth), drawn in ascending id.  depth
+ * (w * h uint16_t) and viz (3 * w * h bytes) may each be NULL.  UVIO_HP_E_ARG: null img, a side < 1, stride < w,
+ * n < 0, n > 0 without ids / uvd. */
+int uvio_hp_debug_loop_depth(const uint8_t *img, int w, int h, int stride, int n, const uint64_t *ids,
+                             const double *uvd, uint16_t *depth, uint8_t *viz);
+/* device milliseconds of the stages of the handle's last uvio_hp_get_track_image / _device call (HIP events on the
+ * library stream): uploads, base, primitives, compose, copy out.  on = 1 switches the event timing on for the
+ * following calls (off by default: each timed call records six events), 0 off; ms may be NULL. */
+int uvio_hp_debug_track_image_times(uvio_hp_t *h, int on, double ms[5]);
 /* the tracker's FAST cells since the handle was created and how many of them had more than 16 candidates
  * (the cells where std::sort's introsort order, not a stable one, decides the selection) */
 int uvio_hp_debug_grid_stats(uvio_hp_t *h, uint64_t *cells, uint64_t *introsort_cells);

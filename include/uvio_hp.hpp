@@ -207,6 +207,62 @@ class Manager {
     return ok != 0;
   }
 
+  // ---- image products (ROS1Visualizer's trackhist and loop-closure depth images) ----
+  // CV_8UC3 data, packed: cv::Mat(height, width, CV_8UC3, data.data()).  overlay: the text display_history would
+  // draw on each camera's image and this library does not (0 "CAM:k", 1 "init", 2 "zvupt"; uvio_hp.h)
+  struct TrackImage {
+    int width = 0, height = 0, overlay = 0;
+    std::vector<uint8_t> data;
+    bool empty() const { return data.empty(); }
+  };
+  // VioManager::get_historical_viz_image; empty before the first camera feed
+  TrackImage get_historical_viz_image() const {
+    TrackImage im;
+    check(uvio_hp_get_track_image(h_, nullptr, 0, &im.width, &im.height, &im.overlay));
+    im.data.resize((size_t)3 * (size_t)im.width * (size_t)im.height);
+    if (!im.data.empty())
+      check(uvio_hp_get_track_image(h_, im.data.data(), im.data.size(), &im.width, &im.height, &im.overlay));
+    return im;
+  }
+  // the same into device memory (cap bytes at out_dev); returns {width, height, overlay} with data left empty
+  TrackImage get_historical_viz_image_device(uint8_t *out_dev, size_t cap) const {
+    TrackImage im;
+    check(uvio_hp_get_track_image_device(h_, out_dev, cap, &im.width, &im.height, &im.overlay));
+    return im;
+  }
+  // Feature::uvs[cam] of one feature, oldest first, with Feature::uvs.size() and Feature::to_delete
+  struct TrackHistory {
+    std::vector<std::array<float, 2>> uv;
+    int n_cams = 0;
+    bool to_delete = false;
+  };
+  TrackHistory track_history(int cam, uint64_t featid) const {
+    TrackHistory th;
+    int n = 0, td = 0;
+    const int rc = uvio_hp_get_track_history(h_, cam, featid, nullptr, 0, &n, &th.n_cams, &td);
+    if (rc != UVIO_HP_E_CAPACITY) check(rc);
+    th.uv.resize((size_t)n);
+    if (n > 0) check(uvio_hp_get_track_history(h_, cam, featid, th.uv[0].data(), n, &n, &th.n_cams, &td));
+    th.to_delete = td != 0;
+    return th;
+  }
+  // the two images of ROS1Visualizer::publish_loopclosure_information for camera 0: depth CV_16UC1, viz CV_8UC3
+  struct LoopDepth {
+    int width = 0, height = 0;
+    double time = -1;
+    std::vector<uint16_t> depth;
+    std::vector<uint8_t> viz;
+  };
+  LoopDepth loop_depth() const {
+    LoopDepth ld;
+    check(uvio_hp_get_loop_depth(h_, nullptr, nullptr, 0, &ld.width, &ld.height, &ld.time));
+    const size_t px = (size_t)ld.width * (size_t)ld.height;
+    ld.depth.resize(px);
+    ld.viz.resize(3 * px);
+    if (px > 0) check(uvio_hp_get_loop_depth(h_, ld.depth.data(), ld.viz.data(), px, &ld.width, &ld.height, &ld.time));
+    return ld;
+  }
+
   // ---- updater-level calls (uvio_hp.h "Updater-level boundary") ----
   void set_state(const std::vector<double> &val, const std::vector<double> &fej, const std::vector<double> &P) {
     const int n = cov_dim();
@@ -293,6 +349,43 @@ inline std::vector<uint8_t> clahe(const uint8_t *img, int w, int h, int stride) 
   std::vector<uint8_t> out(w > 0 && h > 0 ? (size_t)w * (size_t)h : 0);
   const int rc = uvio_hp_debug_clahe(img, w, h, stride, out.data());
   if (rc) throw Error(rc, "uvio_hp_debug_clahe");
+  return out;
+}
+
+// get_historical_viz_image's renderer on caller-given inputs (uvio_hp_debug_draw_tracks): per camera an image (its
+// mask, if any, at the image's stride), its size and its tracks in draw order, whose histories lie in uv ((u, v)
+// pairs); returns the packed CV_8UC3 canvas and its size
+struct DrawCamera {
+  Image image;
+  int width = 0, height = 0;
+  std::vector<uvio_hp_viz_track_t> tracks;
+};
+inline std::vector<uint8_t> draw_tracks(const std::vector<DrawCamera> &cams, const std::vector<float> &uv, int *width,
+                                        int *height) {
+  std::vector<const uint8_t *> imgs, masks;
+  std::vector<int> w, h, strides, counts;
+  std::vector<uvio_hp_viz_track_t> tracks;
+  for (const auto &c : cams) {
+    imgs.push_back(c.image.data);
+    masks.push_back(c.image.mask);
+    strides.push_back(c.image.stride);
+    w.push_back(c.width);
+    h.push_back(c.height);
+    counts.push_back((int)c.tracks.size());
+    tracks.insert(tracks.end(), c.tracks.begin(), c.tracks.end());
+  }
+  int cw = 0, ch = 0;
+  int rc = uvio_hp_debug_draw_tracks((int)cams.size(), imgs.data(), w.data(), h.data(), strides.data(), masks.data(),
+                                     counts.data(), tracks.data(), uv.data(), (int)(uv.size() / 2), nullptr, 0, &cw, &ch,
+                                     nullptr);
+  if (rc) throw Error(rc, "uvio_hp_debug_draw_tracks");
+  std::vector<uint8_t> out((size_t)3 * (size_t)cw * (size_t)ch);
+  rc = uvio_hp_debug_draw_tracks((int)cams.size(), imgs.data(), w.data(), h.data(), strides.data(), masks.data(),
+                                 counts.data(), tracks.data(), uv.data(), (int)(uv.size() / 2), out.data(), out.size(),
+                                 &cw, &ch, nullptr);
+  if (rc) throw Error(rc, "uvio_hp_debug_draw_tracks");
+  if (width) *width = cw;
+  if (height) *height = ch;
   return out;
 }
 

@@ -100,6 +100,12 @@ class FeatResult(C.Structure):
                 ("chi2", C.c_double)]
 
 
+class VizTrack(C.Structure):
+    """uvio_hp_viz_track_t: what display_history reads of one track (uvio_hp_debug_draw_tracks)"""
+    _fields_ = [("id", C.c_uint64), ("u", C.c_float), ("v", C.c_float), ("highlighted", C.c_int),
+                ("n_cams", C.c_int), ("to_delete", C.c_int), ("hist_off", C.c_int), ("hist_n", C.c_int)]
+
+
 _P = C.POINTER
 _D = C.c_double
 _I = C.c_int
@@ -159,6 +165,14 @@ SIGNATURES = [
     ("get_good_features_msckf", _I, [C.c_void_p, _P(_D), _I, _P(_I)]),
     ("odometry_enable", _I, [C.c_void_p, _I]),
     ("fast_state_propagate", _I, [C.c_void_p, _D, _P(_D), _P(_D), _P(_I)]),
+    ("get_track_image", _I, [C.c_void_p, _P(C.c_uint8), C.c_size_t, _P(_I), _P(_I), _P(_I)]),
+    ("get_track_image_device", _I, [C.c_void_p, C.c_void_p, C.c_size_t, _P(_I), _P(_I), _P(_I)]),
+    ("get_track_history", _I, [C.c_void_p, _I, C.c_uint64, _P(C.c_float), _I, _P(_I), _P(_I), _P(_I)]),
+    ("get_loop_depth", _I, [C.c_void_p, _P(C.c_uint16), _P(C.c_uint8), C.c_size_t, _P(_I), _P(_I), _P(_D)]),
+    ("debug_draw_tracks", _I, [_I, _P(_P(C.c_uint8)), _P(_I), _P(_I), _P(_I), _P(_P(C.c_uint8)), _P(_I),
+                               _P(VizTrack), _P(C.c_float), _I, _P(C.c_uint8), C.c_size_t, _P(_I), _P(_I), _P(_D)]),
+    ("debug_loop_depth", _I, [_P(C.c_uint8), _I, _I, _I, _I, _P(C.c_uint64), _P(_D), _P(C.c_uint16), _P(C.c_uint8)]),
+    ("debug_track_image_times", _I, [C.c_void_p, _I, _P(_D)]),
 ]
 
 # uvio_hp_allreduce_fn: int (*)(double *buf, size_t count, void *user)

@@ -26,6 +26,7 @@ SOURCES = [
     "engine_retri.cpp",
     "engine_api.cpp",
     "engine_odom.cpp",
+    "engine_viz.cpp",
     "capi.cpp",
     "shard.cpp",
     "kernels_cov.hip",
@@ -33,6 +34,7 @@ SOURCES = [
     "kernels_feat.hip",
     "kernels_chi2.hip",
     "kernels_track.hip",
+    "kernels_viz.hip",
 ]
 
 

@@ -281,6 +281,58 @@ int uvio_hp_fast_state_propagate(uvio_hp_t *h, double t, double state_plus[13], 
   }
 }
 
+// ---- image products (engine_viz.cpp) ----
+int uvio_hp_get_track_image(uvio_hp_t *h, uint8_t *out, size_t cap, int *width, int *height, int *overlay) {
+  if (!h || !width || !height) return UVIO_HP_E_ARG;
+  HP_GUARD(h, return h->e->track_image(out, cap, width, height, overlay, false);)
+}
+
+int uvio_hp_get_track_image_device(uvio_hp_t *h, uint8_t *out, size_t cap, int *width, int *height, int *overlay) {
+  if (!h || !width || !height) return UVIO_HP_E_ARG;
+  HP_GUARD(h, return h->e->track_image(out, cap, width, height, overlay, true);)
+}
+
+int uvio_hp_get_track_history(uvio_hp_t *h, int cam, uint64_t id, float *uv, int cap, int *n, int *n_cams,
+                              int *to_delete) {
+  if (!h || !n || cap < 0 || (cap > 0 && !uv)) return UVIO_HP_E_ARG;
+  HP_GUARD(h, return h->e->track_history(cam, id, uv, cap, n, n_cams, to_delete);)
+}
+
+int uvio_hp_get_loop_depth(uvio_hp_t *h, uint16_t *depth, uint8_t *viz, size_t cap, int *width, int *height, double *t) {
+  if (!h || !width || !height) return UVIO_HP_E_ARG;
+  HP_GUARD(h, return h->e->loop_depth(depth, viz, cap, width, height, t);)
+}
+
+int uvio_hp_debug_track_image_times(uvio_hp_t *h, int on, double ms[5]) {
+  if (!h) return UVIO_HP_E_ARG;
+  HP_GUARD(h, return h->e->track_image_times(on, ms);)
+}
+
+int uvio_hp_debug_draw_tracks(int ncam, const uint8_t *const *imgs, const int *w, const int *h, const int *strides,
+                              const uint8_t *const *masks, const int *counts, const uvio_hp_viz_track_t *tracks,
+                              const float *uv, int n_uv, uint8_t *out, size_t cap, int *width, int *height,
+                              double *stage_ms) {
+  try {
+    return Engine::draw_tracks_standalone(ncam, imgs, w, h, strides, masks, counts, tracks, uv, n_uv, out, cap, width,
+                                          height, stage_ms);
+  } catch (const HpError &ex) {
+    return ex.code;
+  } catch (...) {
+    return UVIO_HP_E_DEVICE;
+  }
+}
+
+int uvio_hp_debug_loop_depth(const uint8_t *img, int w, int h, int stride, int n, const uint64_t *ids,
+                             const double *uvd, uint16_t *depth, uint8_t *viz) {
+  try {
+    return Engine::loop_depth_standalone(img, w, h, stride, n, ids, uvd, depth, viz);
+  } catch (const HpError &ex) {
+    return ex.code;
+  } catch (...) {
+    return UVIO_HP_E_DEVICE;
+  }
+}
+
 // ---- Updater-level boundary (include/uvio_hp.h) ----
 int uvio_hp_set_state(uvio_hp_t *h, const double *val, const double *fej, int len, const double *P, int N, int ld) {
   if (!h || !val || !fej || !P || len <= 0 || N <= 0) return UVIO_HP_E_ARG;

@@ -408,6 +408,49 @@ struct DeviceBufs {
   Event ev_odom[2];
 };
 
+// The renderer of the image products (engine_viz.cpp): TrackBase::display_history's canvas from device images, host
+// masks and tracks.  Its buffers (canvas, priority plane, primitive table, masks and their pinned mirrors) are made
+// on the first call and grow on demand; a call returns with its output complete, so nothing is in flight when they
+// are replaced.  Nothing here is touched by a feed.
+struct VizCamIn {
+  const uint8_t *img;    // device, rows `stride` bytes apart
+  int w, h, stride;
+  const uint8_t *mask;   // host, rows `mask_stride` bytes apart, or null
+  int mask_stride;
+};
+class VizRenderer {
+ public:
+  // The primitive table of display_history (draw order) for ncam cameras: counts[k] tracks of camera k, concatenated
+  // in tracks, histories in uv.  Returns the number of primitive pixels, -1 if it exceeds an int
+  static long long build_tracks(int ncam, const VizCamIn *cams, const int *counts, const uvio_hp_viz_track_t *tracks,
+                                const float *uv, std::vector<DVizPrim> &prims);
+  // the filled squares of publish_loopclosure_information (camera slot 0) and, if depth is given, its 16-bit map
+  static long long build_depth(int w, int h, int n, const uint64_t *ids, const double *uvd, std::vector<DVizPrim> &prims,
+                               uint16_t *depth);
+  // base + primitives + compose on s, then the canvas (3 * ch * ncam * cw bytes) into out_host, or rendered straight
+  // into out_dev; waits for s
+  void render(hipStream_t s, int ncam, const VizCamIn *cams, const std::vector<DVizPrim> &prims, long long npix,
+              uint8_t *out_host, uint8_t *out_dev);
+  static void cell(int ncam, const VizCamIn *cams, int *cw, int *ch);
+  bool timing = false;
+  double ms[5] = {0, 0, 0, 0, 0};  // uploads, base, primitives, compose, copy out of the last timed call
+
+ private:
+  struct TimedEvent : HipHandle<hipEvent_t, hipEventDestroy> {
+    static TimedEvent create() {
+      TimedEvent e;
+      HP_HIP(hipEventCreate(&e.h_));
+      return e;
+    }
+  };
+  DevBuf<uint8_t> canvas_, d_mask_;
+  DevBuf<unsigned long long> plane_;
+  DevBuf<DVizPrim> d_prims_;
+  PinBuf<DVizPrim> h_prims_;
+  PinBuf<uint8_t> h_mask_, h_out_;
+  TimedEvent ev_[6];
+};
+
 // the per-feature measurement / variable tables of one feature in the reference iteration order (engine_update.cpp)
 class Engine;
 void add_feature(Engine *, const FeatP &f, int mode, int rep, const uvio_hp_options_t &o, const std::vector<DCam> &cams,
@@ -605,7 +648,23 @@ class Engine {
   // Propagator::fast_state_propagate (Propagator.cpp:140-267) from the odometry cache; any thread
   int fast_state_propagate(double t, double *state_plus, double *cov, int *ok);
 
+  // ---- image products (engine_viz.cpp) ----
+  // VioManager::get_historical_viz_image: the canvas into out (host, or device memory with device_out); out null
+  // only reports the size
+  int track_image(uint8_t *out, size_t cap, int *width, int *height, int *overlay, bool device_out);
+  int track_history(int cam, uint64_t id, float *uv, int cap, int *n, int *n_cams, int *to_delete) const;
+  // the two images of ROS1Visualizer::publish_loopclosure_information for camera 0
+  int loop_depth(uint16_t *depth, uint8_t *viz, size_t cap, int *width, int *height, double *t);
+  int track_image_times(int on, double *ms);
+  static int draw_tracks_standalone(int ncam, const uint8_t *const *imgs, const int *w, const int *h,
+                                    const int *strides, const uint8_t *const *masks, const int *counts,
+                                    const uvio_hp_viz_track_t *tracks, const float *uv, int n_uv, uint8_t *out,
+                                    size_t cap, int *width, int *height, double *stage_ms);
+  static int loop_depth_standalone(const uint8_t *img, int w, int h, int stride, int n, const uint64_t *ids,
+                                   const double *uvd, uint16_t *depth, uint8_t *viz);
+
  private:
+  std::unique_ptr<VizRenderer> viz_;  // made by the first image call, never by a feed
   const char *stage_ = "";
   std::vector<double> good_feats_;  // good_features_MSCKF (VioManager.cpp:555-570), 3 per feature
   // The odometry cache.  The feed thread marks it stale where the reference calls invalidate_cache()

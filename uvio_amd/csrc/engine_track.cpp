@@ -1334,6 +1334,23 @@ void Tracker::last_tracks(int cam, std::vector<KeyPt> &pts, std::vector<size_t> 
   ids = it->second.ids_last;
 }
 
+// No predetect_join(), unlike last_pyramid below: the predetect worker only reads cs_, last_cams_, pts_last, ids_last
+// and mask_last (its results go to pre_; a feed, which writes them, joins it first), as last_tracks already relies
+// on, and nothing here waits on a stream, so the tracker's stream selection (cur_) is not touched either.
+int Tracker::viz_cams(VizCam *out) const {
+  std::vector<int> cams = last_cams_;
+  std::sort(cams.begin(), cams.end());
+  int n = 0;
+  for (int cid : cams) {
+    auto it = cs_.find(cid);
+    if (it == cs_.end() || !it->second.have_last || n >= kMaxCams) continue;
+    const CamState &c = it->second;
+    const DPyr &p = c.pyr[c.last];
+    out[n++] = VizCam{cid, p.w[0], p.h[0], p.img[0], &c.mask_last, &c.pts_last, &c.ids_last};
+  }
+  return n;
+}
+
 bool Tracker::last_pyramid(int cam, int level, int *w, int *h, std::vector<uint8_t> *img, std::vector<int16_t> *der) {
   predetect_join();  // its sync() must see the tracker's own stream selection
   auto it = cs_.find(cam);

@@ -451,4 +451,33 @@ struct RansacSlots {
 void launch_ransac(hipStream_t s, const RansacSlots &job, int nslot, int max_iters, double conf,
                    bool undistorted = false);
 
+// ---- image products (kernels_viz.hip; DESIGN.md section 4, "Image products") ----
+// The canvas of TrackBase::display_history: 3-channel u8, ch x (ncam * cw) pixels, camera k's w x h image at x offset
+// k * cw.  The primitives are numbered in the reference's draw order; each covered pixel takes the maximum of
+// (number << 24 | colour) in a 64-bit priority plane (one word per canvas pixel), so "drawn last" wins whatever the
+// schedule, and the compose pass writes the winners over the base.
+enum VizKind { VIZ_DISC1 = 0, VIZ_DISC2 = 1, VIZ_SEG = 2, VIZ_RECT = 3, VIZ_FILL = 4 };
+struct DVizPrim {
+  int first;          // index of its first pixel among all primitive pixels (an exclusive prefix sum)
+  int kind_cam;       // VizKind | camera slot << 8
+  int x0, y0, x1, y1; // disc: centre (x0, y0); segment: the end points; rectangles: the corners, inclusive
+  unsigned colour;    // channel 0 | channel 1 << 8 | channel 2 << 16
+  int i0;             // segment: its first step inside the camera's major-axis range (pixel k is step i0 + k)
+};
+struct VizJob {
+  const uint8_t *img[kMaxCams];   // level 0 of the camera's pyramid (device), rows stride[k] apart
+  const uint8_t *mask[kMaxCams];  // w x h, packed (device), or null
+  int w[kMaxCams], h[kMaxCams], stride[kMaxCams];
+  int ncam, cw, ch;               // the canvas cell
+  uint8_t *canvas;                // 3 * ch * ncam * cw
+  unsigned long long *plane;      // ch * ncam * cw
+  const DVizPrim *prims;
+  int nprim, npix;                // primitives and their pixels in all
+};
+// pixels of a disc (VIZ_DISC1: the 5-pixel plus, VIZ_DISC2: the 21 pixels of the radius-2 midpoint circle's spans)
+constexpr int kVizDiscPixels[2] = {5, 21};
+void launch_viz_base(hipStream_t s, const VizJob &job);
+void launch_viz_prims(hipStream_t s, const VizJob &job);
+void launch_viz_compose(hipStream_t s, const VizJob &job);
+
 }  // namespace uvhp

@@ -45,6 +45,18 @@ class Tracker {
 
   // TrackBase::get_last_obs / get_last_ids for one camera
   void last_tracks(int cam, std::vector<KeyPt> &pts, std::vector<size_t> &ids) const;
+  // what TrackBase::display_history reads of one camera (img_last, img_mask_last, pts_last, ids_last): level 0 of
+  // the last pyramid (device, packed w x h), the last mask (host, empty = none) and the last tracks
+  struct VizCam {
+    int cam, w, h;
+    const uint8_t *img;
+    const std::vector<uint8_t> *mask;
+    const std::vector<KeyPt> *pts;
+    const std::vector<size_t> *ids;
+  };
+  // the cameras of the last feed in ascending camera id; returns their number (0 before the first feed).  The
+  // images were written on the engine's stream: work enqueued there reads them in order, without a host wait
+  int viz_cams(VizCam *out) const;
   // last pyramid level of one camera (img: w*h, der: w*h*2); returns false if absent
   bool last_pyramid(int cam, int level, int *w, int *h, std::vector<uint8_t> *img, std::vector<int16_t> *der);
 

@@ -98,6 +98,7 @@ class VioManager:
 
     def __init__(self, options, device=0):
         self._lib = self._load()
+        self._device = int(device)
         self._h = C.c_void_p()
         rc = self._call("create", C.byref(options), device, C.byref(self._h)) if self._prefix == "uvio_hp_" else \
             self._call("create", C.byref(options), C.byref(self._h))
@@ -495,6 +496,150 @@ class VioManager:
         if rc != 0:  # (the call leaves the handle's error message alone)
             raise RuntimeError("fast_state_propagate failed: %s" % N.ERRNAMES.get(rc, rc))
         return (sp, cov) if ok.value else None
+
+    # ---- image products (ROS1Visualizer's trackhist and loop-closure depth images) ----
+    OVERLAYS = {0: "", 1: "init", 2: "zvupt"}
+
+    def get_track_image(self, device=False):
+        """VioManager::get_historical_viz_image: (canvas uint8 (h, ncam * w, 3), overlay code) -- the canvas of
+        TrackBase::display_history without the text (overlay 0: "CAM:k", 1: "init", 2: "zvupt"); the canvas is
+        (0, 0, 3) before the first camera feed.  device=True: rendered into a torch uint8 tensor on the handle's
+        device and returned as such."""
+        w, h, ov = C.c_int(), C.c_int(), C.c_int()
+        self._check(self._call("get_track_image", self._h, None, 0, C.byref(w), C.byref(h), C.byref(ov)),
+                    "get_track_image")
+        shape = (h.value, w.value, 3)
+        nbytes = 3 * w.value * h.value
+        if nbytes == 0:
+            return np.zeros(shape, dtype=np.uint8), ov.value
+        if device:
+            import torch
+            dev = torch.device("cuda", self._device)  # the handle's device, whatever torch's current one is
+            out = torch.empty(shape, dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize(dev)
+            self._check(self._call("get_track_image_device", self._h, C.c_void_p(out.data_ptr()), nbytes, C.byref(w),
+                                   C.byref(h), C.byref(ov)), "get_track_image_device")
+            return out, ov.value
+        out = np.zeros(shape, dtype=np.uint8)
+        self._check(self._call("get_track_image", self._h, out.ctypes.data_as(C.POINTER(C.c_uint8)), nbytes,
+                               C.byref(w), C.byref(h), C.byref(ov)), "get_track_image")
+        return out, ov.value
+
+    def get_track_history(self, cam, featid):
+        """(uv float32 (n, 2) oldest first, n_cams, to_delete): Feature::uvs[cam], Feature::uvs.size() and
+        Feature::to_delete of one feature of the handle's database; n = 0 when the feature is unknown."""
+        n, nc, td = C.c_int(), C.c_int(), C.c_int()
+        cap = 256
+        while True:
+            uv = np.zeros((cap, 2), dtype=np.float32)
+            rc = self._call("get_track_history", self._h, cam, int(featid), uv.ctypes.data_as(C.POINTER(C.c_float)),
+                            cap, C.byref(n), C.byref(nc), C.byref(td))
+            if rc == N.E_CAPACITY and n.value > cap:
+                cap = n.value
+                continue
+            self._check(rc, "get_track_history")
+            return uv[:n.value].copy(), nc.value, td.value
+
+    def get_loop_depth(self):
+        """The two images of ROS1Visualizer::publish_loopclosure_information for camera 0: (time, depth uint16
+        (h, w), viz uint8 (h, w, 3)); the images are empty when there is no camera-0 image or no active track
+        time yet."""
+        w, h, t = C.c_int(), C.c_int(), C.c_double()
+        self._check(self._call("get_loop_depth", self._h, None, None, 0, C.byref(w), C.byref(h), C.byref(t)),
+                    "get_loop_depth")
+        depth = np.zeros((h.value, w.value), dtype=np.uint16)
+        viz = np.zeros((h.value, w.value, 3), dtype=np.uint8)
+        if depth.size:
+            self._check(self._call("get_loop_depth", self._h, depth.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                   viz.ctypes.data_as(C.POINTER(C.c_uint8)), depth.size, C.byref(w), C.byref(h),
+                                   C.byref(t)), "get_loop_depth")
+        return t.value, depth, viz
+
+    def track_image_times(self, on=True):
+        """Device milliseconds (uploads, base, primitives, compose, copy out) of the last timed get_track_image,
+        and switch the event timing on / off for the following calls."""
+        ms = np.zeros(5)
+        self._check(self._call("debug_track_image_times", self._h, 1 if on else 0, _dp(ms)), "debug_track_image_times")
+        return ms
+
+
+def _strided_u8(img, what):
+    img = np.asarray(img)
+    if img.ndim != 2 or img.dtype != np.uint8:
+        raise ValueError("%s: a 2-D uint8 image" % what)
+    if img.strides[1] != 1 or img.strides[0] < img.shape[1]:
+        img = np.ascontiguousarray(img)
+    return img
+
+
+def draw_tracks(images, tracks, masks=None, stage_ms=False):
+    """uvio_hp_debug_draw_tracks: the renderer of get_track_image on caller-given inputs.  images: per camera a
+    2-D uint8 array (a strided view keeps its row stride); masks: None or per camera None / a uint8 array of the
+    image's shape; tracks: per camera a list, in draw order, of dicts {id, u, v, highlighted, n_cams, to_delete,
+    hist} with hist an (n, 2) array of the feature's (u, v) in this camera, oldest first.  Returns the canvas
+    uint8 (max_h, ncam * max_w, 3) (with stage_ms, also the five device stage times in milliseconds)."""
+    lib = N.load()
+    ncam = len(images)
+    imgs = [_strided_u8(im, "draw_tracks") for im in images]
+    mks = [None] * ncam
+    if masks is not None:
+        for k, m in enumerate(masks):
+            if m is None:
+                continue
+            # (the library reads a mask at its image's stride)
+            buf = np.zeros((imgs[k].shape[0], imgs[k].strides[0]), dtype=np.uint8)
+            buf[:, :imgs[k].shape[1]] = np.asarray(m, dtype=np.uint8)
+            mks[k] = buf
+    bp = C.POINTER(C.c_uint8)
+    ip = C.POINTER(C.c_int)
+    img_p = (bp * ncam)(*[im.ctypes.data_as(bp) for im in imgs])
+    mask_p = (bp * ncam)(*[bp() if m is None else m.ctypes.data_as(bp) for m in mks])
+    ws = np.array([im.shape[1] for im in imgs], dtype=np.int32)
+    hs = np.array([im.shape[0] for im in imgs], dtype=np.int32)
+    st = np.array([im.strides[0] for im in imgs], dtype=np.int32)
+    counts = np.array([len(t) for t in tracks], dtype=np.int32)
+    flat = [t for cam in tracks for t in cam]
+    arr = (N.VizTrack * max(len(flat), 1))()
+    uv = []
+    off = 0
+    for i, t in enumerate(flat):
+        hist = np.asarray(t["hist"], dtype=np.float32).reshape(-1, 2)
+        arr[i] = N.VizTrack(int(t["id"]), float(t["u"]), float(t["v"]), int(t["highlighted"]), int(t["n_cams"]),
+                            int(t["to_delete"]), off, len(hist))
+        uv.append(hist)
+        off += len(hist)
+    uv = np.ascontiguousarray(np.concatenate(uv) if uv else np.zeros((0, 2)), dtype=np.float32)
+    if uv.size == 0:
+        uv = np.zeros((1, 2), dtype=np.float32)
+    w, h = C.c_int(), C.c_int()
+    args = [ncam, img_p, ws.ctypes.data_as(ip), hs.ctypes.data_as(ip), st.ctypes.data_as(ip), mask_p,
+            counts.ctypes.data_as(ip), arr, uv.ctypes.data_as(C.POINTER(C.c_float)), off]
+    N.check(lib.uvio_hp_debug_draw_tracks(*args, None, 0, C.byref(w), C.byref(h), None), what="uvio_hp_debug_draw_tracks")
+    out = np.zeros((h.value, w.value, 3), dtype=np.uint8)
+    ms = np.zeros(5)
+    N.check(lib.uvio_hp_debug_draw_tracks(*args, out.ctypes.data_as(bp), out.size, C.byref(w), C.byref(h),
+                                          _dp(ms) if stage_ms else None), what="uvio_hp_debug_draw_tracks")
+    return (out, ms) if stage_ms else out
+
+
+def loop_depth(img, ids, uvd):
+    """uvio_hp_debug_loop_depth: get_loop_depth's two images on a caller-given 8-bit image and tracks (ids (n,),
+    uvd (n, 3) = u, v, depth) -> (depth uint16 (h, w), viz uint8 (h, w, 3))."""
+    lib = N.load()
+    img = _strided_u8(img, "loop_depth")
+    ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+    uvd = np.ascontiguousarray(uvd, dtype=np.float64).reshape(-1, 3)
+    h, w = img.shape
+    depth = np.zeros((h, w), dtype=np.uint16)
+    viz = np.zeros((h, w, 3), dtype=np.uint8)
+    bp = C.POINTER(C.c_uint8)
+    n = len(ids)
+    rc = lib.uvio_hp_debug_loop_depth(img.ctypes.data_as(bp), w, h, img.strides[0], n,
+                                      ids.ctypes.data_as(C.POINTER(C.c_uint64)) if n else None,
+                                      _dp(uvd) if n else None, depth.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                      viz.ctypes.data_as(bp))
+    N.check(rc, what="uvio_hp_debug_loop_depth")
+    return depth, viz
 
 
 def ekf_update(P, H_index, H, res, sigma2, compressed=False):
