@@ -295,7 +295,8 @@ int uvio_hp_get_good_features_msckf(uvio_hp_t *h, double *xyz_inG, int cap, int 
 /* switch the odometry cache on / off (off by default).  On: the calls after which the reference invalidates its
  * cache (Propagator::invalidate_cache: VioManager.cpp:230, 303, 526, 543, UVioManager.cpp:161 -- a frame that ends
  * in a zero-velocity update or reaches its update stage, uvio_hp_msckf_update, uvio_hp_slam_update) and the calls
- * that set the state (uvio_hp_initialize_with_gt, a static initialization, uvio_hp_set_state, this call) publish
+ * that set the state (uvio_hp_initialize_with_gt, a static initialization, uvio_hp_set_state, this call; an applied
+ * uvio_hp_measurement_update, which has no counterpart inside the reference and is treated as an update) publish
  * the IMU state, its 15 x 15 marginal, calib_camimu_dt and the IMU intrinsics as the cache's next content: one
  * 15 x 15 device gather and a 1.8 KB copy per such call, no host wait.  A frame that returns before its update
  * stage, a propagation, a delayed initialization, uvio_hp_uwb_update_single and the marginalization calls leave the
@@ -405,6 +406,43 @@ int uvio_hp_marginalize_old_clone(uvio_hp_t *h);
  * when the chi2 test passed and the update ran, 0 when it was gated or the anchor is unknown */
 int uvio_hp_uwb_update_single(uvio_hp_t *h, double t, uint64_t anchor_id, double range, int *applied);
 
+/* ---- a measurement of the caller's own (GPS / mocap position, barometer, wheel odometry, magnetometer ...) ----
+ * The two reference surfaces uvio itself used to add UWB from outside the estimator: move the filter to the
+ * measurement's time, then one StateHelper::EKFUpdate with the caller's Jacobian, residual and noise matrix.
+ * The sequence is propagate -> uvio_hp_get_state_vector (values and meta) -> build H and res -> update. */
+/* UVioPropagator::propagate (UVioPropagator.cpp:27-115): the state and covariance to time t (IMU clock) with the
+ * IMU readings fed so far, without a clone.  The reference's two quirks are kept: the end time carries no
+ * camera-IMU time offset, and last_prop_time_offset is not updated.  UVIO_HP_E_ORDER when t is not after the
+ * state time (the state is untouched), UVIO_HP_E_STATE before initialization.  The odometry cache is left alone,
+ * as by uvio_hp_propagate_and_clone. */
+int uvio_hp_propagate(uvio_hp_t *h, double t);
+/* StateHelper::EKFUpdate(state, H_order, H, res, R) (StateHelper.h:88, StateHelper.cpp:116-197) behind the chi2
+ * test of UpdaterUWB.cpp:67-79.  H_order is the block list: block k of H's columns is the covariance range
+ * [ids[k], ids[k] + sizes[k]) (uvio_hp_get_state_vector's meta; any order, repeats allowed, as for
+ * uvio_hp_get_marginal_cov).  H is r x n (row-major, leading dimension ldh), n = sum sizes, with respect to the
+ * error state: the JPL left quaternion error for orientations, each landmark's own parametrization.  res is the
+ * r residuals, R the r x r noise matrix (leading dimension ldr) of which only the upper triangle is read
+ * (S.triangularView<Upper>() += R, StateHelper.cpp:156).
+ * Gate: S = H P_II H^T + R, chi2 = res^T S^-1 res; the update runs iff chi2 is not above chi2_thr (INFINITY: no
+ * gate; for the reference's updaters chi2_thr = chi2_multipler * uvio_hp_chi2_95(r)).  Accepted: the covariance is
+ * updated on the device (P -= (M L^-T)(M L^-T)^T, S = L L^T, the kernels of every other update) and dx = K res
+ * moves the mean through Type::update (values only; first estimates stay).  One readback, one host wait.
+ * *chi2 and *applied are written whenever the call returns 0; dx (optional, N doubles, N = uvio_hp_get_cov_dim)
+ * receives the correction, zeros when the update was not applied.  r == 0 or nvar == 0 does nothing (*applied = 0).
+ * UVIO_HP_E_ARG, before any device work: null pointers, nvar < 0, a size < 1, a block outside [0, N), ldh < n,
+ * ldr < r, a chi2_thr that is not positive (or NaN), a non-finite entry of H, res or the read triangle of R.
+ * UVIO_HP_E_CAPACITY, before any device work: r > 255 rows or n > 1215 columns (uvio_hp_ekf_update's limits), or
+ * an H larger than the upload staging ring.
+ * UVIO_HP_E_ARG after the factorization: S is not positive definite (a pivot of its LDL^T factor is not a finite
+ * positive number; uvio_hp_last_error says so); covariance and mean are untouched and the handle stays usable.
+ * UVIO_HP_E_NUMERIC (fatal, as everywhere): a negative covariance diagonal after an accepted update.
+ * Serialized with the feeds.  When applied the odometry cache is republished, as after uvio_hp_msckf_update.
+ * Not covered: state variables of the caller's own (a sensor bias or lever arm), buffering such measurements
+ * inside uvio_hp_feed_camera as UWB messages are, and chains of relinearized updates on the device. */
+int uvio_hp_measurement_update(uvio_hp_t *h, int nvar, const int *ids, const int *sizes, const double *H, int ldh, int r,
+                               const double *res, const double *R, int ldr, double chi2_thr, double *chi2, int *applied,
+                               double *dx);
+
 /* ---- feature-sharded MSCKF update across GPUs (BASELINE.json configs 4-5) ----
  * One process per GPU, each with its own handle fed the same measurement stream (the filter state is
  * replicated).  Inside UpdaterMSCKF::update (UpdaterMSCKF.cpp:58-295) the selected features are split into
@@ -449,6 +487,18 @@ int uvio_hp_debug_frame_feats(uvio_hp_t *h, int *kind, uint64_t *ids, double *pG
  * reference exits; P and dx_out hold the update all the same). */
 int uvio_hp_ekf_update(double *P, int N, const int *H_index, int n, const double *H, int r,
                        const double *res, double sigma2, double *dx_out);
+/* StateHelper::EKFUpdate (StateHelper.cpp:116-197) with a dense noise matrix on a standalone covariance, behind
+ * the chi2 gate of UpdaterUWB.cpp:67-79: uvio_hp_ekf_update's arguments and limits with R (r x r, leading
+ * dimension ldr, upper triangle read) in place of sigma2, and the gate of uvio_hp_measurement_update (the same
+ * three kernels).  *chi2 and *applied are written when the call returns 0.  Not applied: P comes back unchanged
+ * and dx_out is zeros.  UVIO_HP_E_ARG also for ldr < r, a chi2_thr that is not positive, non-finite inputs, and an
+ * S that is not positive definite (uvio_hp_last_error(NULL) says so). */
+int uvio_hp_ekf_update_r(double *P, int N, const int *H_index, int n, const double *H, int r, const double *res,
+                         const double *R, int ldr, double chi2_thr, double *dx_out, double *chi2, int *applied);
+/* boost::math::quantile(chi_squared(dof), 0.95), the table every reference updater multiplies its chi2_multipler
+ * into (UpdaterMSCKF.cpp:52-55, UpdaterSLAM.cpp:55-58, UpdaterZeroVelocity.cpp:59-62, UpdaterUWB.h:33-36), for
+ * dof 1 .. 999; UVIO_HP_E_ARG outside that range. */
+int uvio_hp_chi2_95(int dof, double *thr);
 /* UpdaterMSCKF.cpp:274-286: measurement_compress_inplace of the stacked [H | res] (m x n) followed by
  * StateHelper::EKFUpdate on the compressed rows, on a standalone covariance (same arguments as
  * uvio_hp_ekf_update).  When m > n the device runs the update in information form on H^T H, H^T res

@@ -12,11 +12,14 @@
  *   Manager::slam_change_anchors   <- UpdaterSLAM::change_anchors (UpdaterSLAM.h:87)
  *   Manager::uwb_update_single     <- UpdaterUWB::update_single (UpdaterUWB.h:55)
  *   Manager::propagate_and_clone   <- Propagator::propagate_and_clone (Propagator.h:110)
+ *   Manager::propagate             <- UVioPropagator::propagate (UVioPropagator.cpp:27)
+ *   Manager::measurement_update    <- StateHelper::EKFUpdate (StateHelper.h:88) behind UpdaterUWB.cpp:67-79's gate
  */
 #ifndef UVIO_HP_HPP
 #define UVIO_HP_HPP
 
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -44,6 +47,42 @@ struct Feature {
   uint64_t featid = 0;
   std::vector<uvio_hp_feat_meas_t> meas;
 };
+
+// JPL quaternion (x, y, z, w) -> rotation matrix, row-major (ov_core quat_ops.h quat_2_Rot)
+inline std::array<double, 9> quat_2_Rot(const double q[4]) {
+  const double x = q[0], y = q[1], z = q[2], w = q[3], c = 2.0 * w * w - 1.0;
+  return {c + 2.0 * x * x,         2.0 * (x * y + w * z),   2.0 * (x * z - w * y),
+          2.0 * (x * y - w * z),   c + 2.0 * y * y,         2.0 * (y * z + w * x),
+          2.0 * (x * z + w * y),   2.0 * (y * z - w * x),   c + 2.0 * z * z};
+}
+
+// A position sensor S mounted at p_SinI in the IMU frame that measures its own position in the global frame:
+// h(x) = p_IinG + R_GtoI^T p_SinI.  Over the IMU pose's error state [dtheta, dp] (JPL left error,
+// R(dtheta (x) q) ~ (I - [dtheta]x) R): H_theta = -R_GtoI^T [p_SinI]x, H_p = I.  imu: Manager::imu_value's first
+// 7 numbers; h (3) and H (3 x 6, row-major) are written.
+inline void position_fix_jacobian(const double imu[7], const std::array<double, 3> &p_SinI, double h[3], double H[18]) {
+  const std::array<double, 9> R = quat_2_Rot(imu);
+  const double s[3] = {p_SinI[0], p_SinI[1], p_SinI[2]};
+  const double S[9] = {0.0, -s[2], s[1], s[2], 0.0, -s[0], -s[1], s[0], 0.0};
+  for (int i = 0; i < 3; i++) {
+    h[i] = imu[4 + i];
+    for (int k = 0; k < 3; k++) h[i] += R[(size_t)(3 * k + i)] * s[k];
+    for (int j = 0; j < 3; j++) {
+      double a = 0.0;
+      for (int k = 0; k < 3; k++) a += R[(size_t)(3 * k + i)] * S[3 * k + j];
+      H[6 * i + j] = -a;
+      H[6 * i + 3 + j] = i == j ? 1.0 : 0.0;
+    }
+  }
+}
+
+// the reference's 95 % chi-squared table (chi2_multipler's factor), dof 1 .. 999
+inline double chi2_95(int dof) {
+  double v = 0.0;
+  const int rc = uvio_hp_chi2_95(dof, &v);
+  if (rc) throw Error(rc, "uvio_hp_chi2_95: dof outside 1 .. 999");
+  return v;
+}
 
 class Manager {
  public:
@@ -286,6 +325,64 @@ class Manager {
     int applied = 0;
     check(uvio_hp_uwb_update_single(h_, t, anchor_id, range, &applied));
     return applied != 0;
+  }
+
+
+  // ---- a measurement of the caller's own: propagate -> read the state -> build H -> update ----
+  // UVioPropagator::propagate: the state to time t (IMU clock) without a clone
+  void propagate(double t) { check(uvio_hp_propagate(h_, t)); }
+  // (kind, covariance id, size) of every state variable, in state_vector()'s order
+  std::vector<std::array<int, 3>> state_meta() const {
+    std::vector<double> x(8192);
+    std::vector<int> meta(3 * 2048);
+    int len = 0, nv = 0;
+    check(uvio_hp_get_state_vector(h_, x.data(), (int)x.size(), &len, meta.data(), (int)meta.size(), &nv));
+    std::vector<std::array<int, 3>> out;
+    for (int k = 0; k < nv && 3 * k + 2 < (int)meta.size(); k++)
+      out.push_back({meta[(size_t)3 * k], meta[(size_t)3 * k + 1], meta[(size_t)3 * k + 2]});
+    return out;
+  }
+  struct MeasurementResult {
+    bool applied = false;
+    double chi2 = 0.0;
+    std::vector<double> dx;  // cov_dim() numbers, zeros when the update was gated
+  };
+  // StateHelper::EKFUpdate(state, H_order, H, res, R) behind a chi2 gate: blocks = (covariance id, size) of H's column
+  // blocks (state_meta), H row-major res.size() x (sum of the sizes) over the error state, R row-major
+  // res.size() x res.size() of which the upper triangle is read; chi2_thr = INFINITY: no gate
+  MeasurementResult measurement_update(const std::vector<std::pair<int, int>> &blocks, const std::vector<double> &H,
+                                       const std::vector<double> &res, const std::vector<double> &R,
+                                       double chi2_thr = INFINITY) {
+    std::vector<int> ids, sizes;
+    size_t n = 0;
+    for (const auto &b : blocks) {
+      ids.push_back(b.first);
+      sizes.push_back(b.second);
+      if (b.second > 0) n += (size_t)b.second;
+    }
+    const size_t r = res.size();
+    if (H.size() != r * n || R.size() != r * r) throw Error(UVIO_HP_E_ARG, "measurement_update: size mismatch");
+    MeasurementResult out;
+    out.dx.assign((size_t)cov_dim(), 0.0);
+    int applied = 0;
+    check(uvio_hp_measurement_update(h_, (int)blocks.size(), ids.data(), sizes.data(), H.data(), (int)n, (int)r,
+                                     res.data(), R.data(), (int)r, chi2_thr, &out.chi2, &applied, out.dx.data()));
+    out.applied = applied != 0;
+    return out;
+  }
+  // one worked measurement: a global position fix p_meas of a sensor at p_SinI (position_fix_jacobian), noise R
+  // (3 x 3 row-major), linearized at the current values and gated at chi2_mult * chi2_95(3)
+  MeasurementResult position_fix(const std::array<double, 3> &p_meas, const std::array<double, 3> &p_SinI,
+                                 const std::array<double, 9> &R, double chi2_mult = 1.0) {
+    const std::array<double, 16> x = imu_value();
+    double h[3], H[18];
+    position_fix_jacobian(x.data(), p_SinI, h, H);
+    int imu_id = 0;
+    for (const auto &m : state_meta())
+      if (m[0] == 0) imu_id = m[1];  // kind 0: the IMU; its pose is its first 6 columns
+    return measurement_update({{imu_id, 6}}, std::vector<double>(H, H + 18),
+                              {p_meas[0] - h[0], p_meas[1] - h[1], p_meas[2] - h[2]},
+                              std::vector<double>(R.begin(), R.end()), chi2_mult * chi2_95(3));
   }
 
   uvio_hp_t *handle() { return h_; }

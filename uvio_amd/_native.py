@@ -173,6 +173,11 @@ SIGNATURES = [
                                _P(VizTrack), _P(C.c_float), _I, _P(C.c_uint8), C.c_size_t, _P(_I), _P(_I), _P(_D)]),
     ("debug_loop_depth", _I, [_P(C.c_uint8), _I, _I, _I, _I, _P(C.c_uint64), _P(_D), _P(C.c_uint16), _P(C.c_uint8)]),
     ("debug_track_image_times", _I, [C.c_void_p, _I, _P(_D)]),
+    ("propagate", _I, [C.c_void_p, _D]),
+    ("measurement_update", _I, [C.c_void_p, _I, _P(_I), _P(_I), _P(_D), _I, _I, _P(_D), _P(_D), _I, _D, _P(_D), _P(_I),
+                                _P(_D)]),
+    ("ekf_update_r", _I, [_P(_D), _I, _P(_I), _I, _P(_D), _I, _P(_D), _P(_D), _I, _D, _P(_D), _P(_D), _P(_I)]),
+    ("chi2_95", _I, [_I, _P(_D)]),
 ]
 
 # uvio_hp_allreduce_fn: int (*)(double *buf, size_t count, void *user)

@@ -375,6 +375,17 @@ int uvio_hp_uwb_update_single(uvio_hp_t *h, double t, uint64_t anchor_id, double
   HP_FEED(h, h->e->api_uwb_update_single(anchor_id, range, applied))
 }
 
+int uvio_hp_propagate(uvio_hp_t *h, double t) {
+  if (!h) return UVIO_HP_E_ARG;
+  HP_FEED(h, h->e->api_propagate(t))
+}
+int uvio_hp_measurement_update(uvio_hp_t *h, int nvar, const int *ids, const int *sizes, const double *H, int ldh, int r,
+                               const double *res, const double *R, int ldr, double chi2_thr, double *chi2, int *applied,
+                               double *dx) {
+  if (!h) return UVIO_HP_E_ARG;
+  HP_FEED(h, h->e->api_measurement_update(nvar, ids, sizes, H, ldh, r, res, R, ldr, chi2_thr, chi2, applied, dx))
+}
+
 int uvio_hp_debug_last_msckf(uvio_hp_t *h, uint64_t *ids, double *pG, int *status, double *chi2, int cap, int *n) {
   if (!h || !n) return UVIO_HP_E_ARG;
   const auto &v = h->e->last_msckf_;
@@ -444,6 +455,24 @@ int uvio_hp_ekf_update(double *P, int N, const int *H_index, int n, const double
   } catch (...) {
     return UVIO_HP_E_DEVICE;
   }
+}
+
+int uvio_hp_ekf_update_r(double *P, int N, const int *H_index, int n, const double *H, int r, const double *res,
+                         const double *R, int ldr, double chi2_thr, double *dx_out, double *chi2, int *applied) {
+  try {
+    return Engine::ekf_update_R_standalone(P, N, H_index, n, H, r, res, R, ldr, chi2_thr, dx_out, chi2, applied);
+  } catch (const HpError &ex) {
+    g_create_err = ex.what();  // (no handle: uvio_hp_last_error(NULL) on this thread)
+    return ex.code;
+  } catch (...) {
+    return UVIO_HP_E_DEVICE;
+  }
+}
+
+int uvio_hp_chi2_95(int dof, double *thr) {
+  if (!thr || dof < 1 || dof > 999) return UVIO_HP_E_ARG;
+  *thr = chi2_quantile95(dof);
+  return 0;
 }
 
 int uvio_hp_msckf_compressed_update(double *P, int N, const int *H_index, int n, const double *H, int m,

@@ -459,6 +459,8 @@ void add_feature(Engine *, const FeatP &f, int mode, int rep, const uvio_hp_opti
 // algorithmic FP64 FLOPs / bytes of one EKFUpdate (engine_state.cpp)
 double ekf_flops(double N, double n, double r);
 double ekf_bytes(double N, double n, double r);
+// a caller's H (r x n, ld ldh), res (r) and the upper triangle of R (r x r, ld ldr) hold finite numbers only
+bool ekf_R_inputs_finite(const double *H, int ldh, int r, int n, const double *res, const double *R, int ldr);
 
 class Engine {
  public:
@@ -500,6 +502,10 @@ class Engine {
   void shard_init_host(int rank, int world, uvio_hp_allreduce_fn fn, void *user, int min_features);
 
   // standalone kernel-level entry points (parity tests)
+  // ekf_update_standalone's direct form with a dense R and a chi2 gate (launch_ekf_update_R)
+  static int ekf_update_R_standalone(double *P, int N, const int *H_index, int n, const double *H, int r,
+                                     const double *res, const double *R, int ldr, double chi2_thr, double *dx_out,
+                                     double *chi2, int *applied);
   static int ekf_update_standalone(double *P, int N, const int *H_index, int n, const double *H, int r, const double *res,
                                    double sigma2, double *dx_out, bool compress = false);
   static int compress_standalone(const double *A, int m, int n, double *R_out);
@@ -635,6 +641,13 @@ class Engine {
   int api_marginalize_slam();
   int api_marginalize_old_clone();
   int api_uwb_update_single(uint64_t anchor_id, double range, int *applied);
+  // UVioPropagator::propagate (UVioPropagator.cpp:27-115): the state to t without a clone (propagate_uwb)
+  int api_propagate(double t);
+  // StateHelper::EKFUpdate (StateHelper.cpp:116-197) of a caller's H, residual and dense R over the given blocks of
+  // the state, behind the chi2 gate of UpdaterUWB.cpp:67-79 (launch_ekf_update_R); dx moves the mean when applied
+  int api_measurement_update(int nvar, const int *ids, const int *sizes, const double *H, int ldh, int r,
+                             const double *res, const double *R, int ldr, double chi2_thr, double *chi2, int *applied,
+                             double *dx);
   // the reference routine the host was in when the last call failed (error messages)
   const char *stage() const { return stage_; }
 

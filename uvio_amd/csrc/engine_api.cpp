@@ -134,4 +134,93 @@ int Engine::api_uwb_update_single(uint64_t anchor_id, double range, int *applied
   return 0;
 }
 
+// UVioPropagator::propagate (UVioPropagator.cpp:27-115): Engine::propagate_uwb with its two quirks (the end time
+// carries no camera-IMU offset, last_prop_time_offset stays).  No clone, and the odometry cache is left alone, as
+// after propagate_and_clone.
+int Engine::api_propagate(double t) {
+  if (!is_initialized_) throw HpError(UVIO_HP_E_STATE, "propagate before initialization");
+  if (!(timestamp_ < t)) return UVIO_HP_E_ORDER;
+  return propagate_uwb(t);
+}
+
+// StateHelper::EKFUpdate(state, H_order, H, res, R) (StateHelper.cpp:116-197) behind the chi2 test of
+// UpdaterUWB.cpp:67-79, for a measurement of the caller's: H_order is the list of covariance blocks.  H with the
+// residual as its last column, R's upper triangle and the column map go up as one staged table; the three launches of
+// launch_ekf_update_R follow and one readback returns [negative diagonals | dx | chi2, accepted]: one host wait,
+// as in ekf_update_rows.  Every refusal but the positive-definiteness one comes before any device work.
+int Engine::api_measurement_update(int nvar, const int *ids, const int *sizes, const double *H, int ldh, int r,
+                                   const double *res, const double *R, int ldr, double chi2_thr, double *chi2,
+                                   int *applied, double *dx) {
+  if (!is_initialized_) throw HpError(UVIO_HP_E_STATE, "measurement update before initialization");
+  stage_ = "StateHelper::EKFUpdate (measurement_update)";
+  if (!chi2 || !applied || nvar < 0 || r < 0) return UVIO_HP_E_ARG;
+  if (!(chi2_thr > 0.0)) throw HpError(UVIO_HP_E_ARG, "measurement_update: the chi2 threshold must be positive");
+  if (nvar > 0 && (!ids || !sizes)) return UVIO_HP_E_ARG;
+  long long nl = 0;
+  for (int k = 0; k < nvar; k++) {
+    if (sizes[k] < 1 || ids[k] < 0 || (long long)ids[k] + sizes[k] > N_)
+      throw HpError(UVIO_HP_E_ARG, "measurement_update: a block lies outside the state");
+    nl += sizes[k];
+  }
+  if (nvar == 0 || r == 0) {
+    *chi2 = 0.0;
+    *applied = 0;
+    if (dx) std::fill(dx, dx + N_, 0.0);
+    return 0;
+  }
+  if (!H || !res || !R) return UVIO_HP_E_ARG;
+  if (ldh < nl || ldr < r) throw HpError(UVIO_HP_E_ARG, "measurement_update: leading dimension below the row length");
+  if (r > kMaxEkfRows) throw HpError(UVIO_HP_E_CAPACITY, "measurement_update: more than 255 rows");
+  if (nl > 1215) throw HpError(UVIO_HP_E_CAPACITY, "measurement_update: more than 1215 columns");
+  const int n = (int)nl;
+  if (!ekf_R_inputs_finite(H, ldh, r, n, res, R, ldr))
+    throw HpError(UVIO_HP_E_ARG, "measurement_update: H, res or the upper triangle of R is not finite");
+  const int ldd = n + 1;
+  const size_t nH = (size_t)r * ldd, nR = (size_t)r * r;
+  const size_t bytes = sizeof(double) * (nH + nR) + sizeof(int) * (size_t)n;
+  if ((bytes + 255) / 256 * 256 > d_.stg_cap)
+    throw HpError(UVIO_HP_E_CAPACITY, "measurement_update: H does not fit the upload staging ring");
+  void *hv = nullptr;
+  double *dH = (double *)stage_reserve(bytes, &hv);
+  double *hH = (double *)hv, *hR = hH + nH;
+  int *hI = (int *)(hR + nR);
+  for (int i = 0; i < r; i++) {
+    std::memcpy(hH + (size_t)i * ldd, H + (size_t)i * ldh, sizeof(double) * n);
+    hH[(size_t)i * ldd + n] = res[i];
+    for (int j = 0; j < r; j++) hR[(size_t)i * r + j] = j >= i ? R[(size_t)i * ldr + j] : 0.0;
+  }
+  for (int k = 0, c = 0; k < nvar; k++)
+    for (int i = 0; i < sizes[k]; i++) hI[c++] = ids[k] + i;
+  const double *dR = dH + nH;
+  const int *dI = (const int *)(dR + nR);
+  stage_flush();
+  EkfScratch sc = d_.ekf;
+  sc.Tall = nullptr;
+  sc.kmask_tile = nullptr;
+  sc.gate = nullptr;
+  sc.chi2_gate = (int *)(sc.dx + N_ + 2);  // behind [chi2, accepted]; the dx block holds cap + 15 doubles
+  {
+    KScope ks(&kprof_, KC_EKF);
+    launch_ekf_update_R(d_.stream, d_.P, d_.ldp, N_, dH, ldd, r, n, dI, dH + n, ldd, dR, r, chi2_thr, sc);
+    ++p_epoch_;
+  }
+  kprof_.credit(KC_EKF, ekf_flops(N_, n, r), ekf_bytes(N_, n, r));
+  read_dx("measurement_update");
+  const double c2 = d_.dx_host[N_];
+  const bool acc = d_.dx_host[N_ + 1] != 0.0;
+  *chi2 = c2;
+  *applied = acc ? 1 : 0;
+  if (!acc) {
+    if (dx) std::fill(dx, dx + N_, 0.0);
+    if (!std::isfinite(c2))
+      throw HpError(UVIO_HP_E_ARG, "measurement_update: S = H P H^T + R is not positive definite; nothing was applied");
+    return 0;
+  }
+  apply_dx(d_.dx_host);
+  if (dx) std::memcpy(dx, d_.dx_host, sizeof(double) * N_);
+  odom_invalidate();  // as after UpdaterMSCKF::update (VioManager.cpp:526)
+  odom_flush();
+  return 0;
+}
+
 }  // namespace uvhp

@@ -783,6 +783,73 @@ int Engine::ekf_update_standalone(double *P, int N, const int *H_index, int n, c
   return neg > 0 ? UVIO_HP_E_NUMERIC : 0;
 }
 
+// H (r x n, ld ldh), res (r) and the upper triangle of R (r x r, ld ldr) hold finite numbers only
+bool ekf_R_inputs_finite(const double *H, int ldh, int r, int n, const double *res, const double *R, int ldr) {
+  for (int i = 0; i < r; i++) {
+    for (int j = 0; j < n; j++)
+      if (!std::isfinite(H[(size_t)i * ldh + j])) return false;
+    if (!std::isfinite(res[i])) return false;
+    for (int j = i; j < r; j++)
+      if (!std::isfinite(R[(size_t)i * ldr + j])) return false;
+  }
+  return true;
+}
+
+// ekf_update_standalone's direct form with the caller's dense R (upper triangle) and the chi2 gate on the update's
+// own factor (launch_ekf_update_R): the same buffers and checks.  Not applied (gated, or S not positive definite:
+// UVIO_HP_E_ARG): P is not written and dx_out is zeros.
+int Engine::ekf_update_R_standalone(double *P, int N, const int *H_index, int n, const double *H, int r,
+                                    const double *res, const double *R, int ldr, double chi2_thr, double *dx_out,
+                                    double *chi2, int *applied) {
+  if (!P || N <= 0 || n <= 0 || r <= 0 || !H || !res || !H_index || !dx_out || !R || !chi2 || !applied)
+    return UVIO_HP_E_ARG;
+  if (ldr < r || !(chi2_thr > 0.0)) return UVIO_HP_E_ARG;
+  for (int j = 0; j < n; j++)
+    if (H_index[j] < 0 || H_index[j] >= N) return UVIO_HP_E_ARG;
+  if (r > kMaxEkfRows) return UVIO_HP_E_CAPACITY;
+  if ((size_t)16 * (n | 1) * sizeof(double) > (size_t)kMaxDynLds) return UVIO_HP_E_CAPACITY;
+  if (!ekf_R_inputs_finite(H, n, r, n, res, R, ldr)) return UVIO_HP_E_ARG;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return UVIO_HP_E_DEVICE;
+  Stream s = Stream::create();
+  const int ldh = n + 1;
+  DevBuf<double> dP((size_t)N * N), dH((size_t)r * ldh), dR((size_t)r * r);
+  DevBuf<double> dM((size_t)N * r), dW((size_t)N * r), dS((size_t)5 * r * r), dy(r), dDinv((size_t)(r / 16 + 1) * 256);
+  DevBuf<double> ddx((size_t)N + 2);  // [dx | chi2, accepted]
+  DevBuf<int> dI(n), dneg(2);         // [negative diagonals, gate]
+  std::vector<double> Ha((size_t)r * ldh), Ru((size_t)r * r, 0.0);
+  for (int i = 0; i < r; i++) {
+    std::memcpy(&Ha[(size_t)i * ldh], H + (size_t)i * n, sizeof(double) * n);
+    Ha[(size_t)i * ldh + n] = res[i];
+    for (int j = i; j < r; j++) Ru[(size_t)i * r + j] = R[(size_t)i * ldr + j];
+  }
+  HP_HIP(hipMemcpyAsync(dP, P, sizeof(double) * N * N, hipMemcpyHostToDevice, s));
+  HP_HIP(hipMemcpyAsync(dH, Ha.data(), sizeof(double) * Ha.size(), hipMemcpyHostToDevice, s));
+  HP_HIP(hipMemcpyAsync(dR, Ru.data(), sizeof(double) * Ru.size(), hipMemcpyHostToDevice, s));
+  HP_HIP(hipMemcpyAsync(dI, H_index, sizeof(int) * n, hipMemcpyHostToDevice, s));
+  HP_HIP(hipMemsetAsync(dneg, 0, 2 * sizeof(int), s));
+  EkfScratch sc{dM, dW, dS, dy, ddx, dneg, dDinv};
+  sc.chi2_gate = dneg + 1;
+  launch_ekf_update_R(s, dP, N, N, dH, ldh, r, n, dI, dH + n, ldh, dR, r, chi2_thr, sc);
+  int neg = 0;
+  double g[2] = {0.0, 0.0};
+  HP_HIP(hipMemcpyAsync(g, ddx + N, sizeof(g), hipMemcpyDeviceToHost, s));
+  HP_HIP(hipMemcpyAsync(&neg, dneg, sizeof(int), hipMemcpyDeviceToHost, s));
+  HP_HIP(hipStreamSynchronize(s));
+  *chi2 = g[0];
+  *applied = g[1] != 0.0 ? 1 : 0;
+  if (!*applied) {
+    std::fill(dx_out, dx_out + N, 0.0);
+    if (!std::isfinite(g[0]))
+      throw HpError(UVIO_HP_E_ARG, "ekf_update_R: S = H P H^T + R is not positive definite; nothing was applied");
+    return 0;
+  }
+  HP_HIP(hipMemcpyAsync(P, dP, sizeof(double) * N * N, hipMemcpyDeviceToHost, s));
+  HP_HIP(hipMemcpyAsync(dx_out, ddx, sizeof(double) * N, hipMemcpyDeviceToHost, s));
+  HP_HIP(hipStreamSynchronize(s));  // nothing in flight when the buffers go
+  return neg > 0 ? UVIO_HP_E_NUMERIC : 0;
+}
+
 // Standalone measurement compression: R factor of [H | res] (m x (n+1)) via the Gram + Cholesky kernels
 int Engine::compress_standalone(const double *A, int m, int n, double *R_out) {
   if (!A || m <= 0 || n <= 0 || !R_out) return UVIO_HP_E_ARG;

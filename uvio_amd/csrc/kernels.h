@@ -253,6 +253,15 @@ void launch_ekf_phaseA(hipStream_t s, const double *P, int ldp, int N, const dou
                        const int *hidx, double sigma2, EkfScratch &sc);
 void launch_ekf_phaseB(hipStream_t s, double *P, int ldp, int N, int r, const double *res, int res_stride,
                        EkfScratch &sc);
+// The same update with a caller's dense noise matrix R (r x r, ld ldr, device; only its upper triangle is read, as
+// S.triangularView<Upper>() += R, StateHelper.cpp:156) behind a chi2 gate on the update's own factor
+// (UpdaterUWB.cpp:67-79): phase A with sigma2 = 0, then k_ekf_fact_R, then k_ekf_WP behind the gate.
+// sc.chi2_gate (required; its incoming value is not read) receives accepted = every pivot of S finite and > 0,
+// chi2 = res^T S^-1 res finite and not above chi2_thr; [chi2, accepted] go to sc.dx[N], sc.dx[N + 1], chi2 as NaN
+// when a pivot is bad.  Not accepted: P and sc.dx[0 .. N) are left as they were.  sc.Tall must be null.
+void launch_ekf_update_R(hipStream_t s, double *P, int ldp, int N, const double *H, int ldh, int r, int n,
+                         const int *hidx, const double *res, int res_stride, const double *R, int ldr, double chi2_thr,
+                         EkfScratch &sc);
 // the JPL pose value behind a clone / camera-extrinsic table entry (PoseJPL: q_GtoI / q_ItoC, position) and its
 // covariance id, updated on the device inside a delayed-initialization chain
 struct DPoseVal {

@@ -190,6 +190,77 @@ __global__ void __launch_bounds__(kFactThreads) k_ekf_fact(const double *__restr
 }
 size_t ekf_small_lds_bytes(int r) { return (dense_lds_bytes(r + 1, r) + (size_t)2 * r * sizeof(double)); }
 
+// K2 for a caller's dense noise matrix (launch_ekf_update_R): k_ekf_fact on S = S_up + R, where S_up = H P_II H^T
+// comes from k_ekf_MS with s2 = 0 and only R's upper triangle (r x r, ld ldr, device) is read, as the reference's
+// S.triangularView<Upper>() += R (StateHelper.cpp:156).  With R = s2 I the staged values are k_ekf_MS's own
+// (acc + 0.0) + s2, so the factor, L^-1 and y are those of k_ekf_fact bit for bit.
+// A caller's R can make S indefinite, and a NaN chi2 must not pass the gate as it does in k_ekf_fact: every pivot
+// Dd[k] has to be finite and > 0 and chi2 = |y|^2 (k_ekf_fact's summation order) finite.
+//   accepted = pivots_ok && isfinite(chi2) && !(chi2 > thr)  ->  *gate (k_ekf_WP's gate), [chi2, accepted] -> gate_out
+// with chi2 written as NaN when a pivot is bad.
+template <int W, bool LDS>
+__global__ void __launch_bounds__(kFactThreads) k_ekf_fact_R(const double *__restrict__ Sup, int r,
+                                                    const double *__restrict__ R, int ldr,
+                                                    const double *__restrict__ res, int res_stride,
+                                                    double *__restrict__ Linv_out, double *__restrict__ y_out, double *Sg,
+                                                    int *gate, double chi2_thr, double *__restrict__ gate_out) {
+  extern __shared__ double lds[];
+  double *A = LDS ? lds : Sg;
+  const int ld = r | 1;
+  double *Dd = A + (size_t)(r + 1) * ld, *sd = Dd + r;
+  staged_copy(
+      r * r + r,
+      [&](int e) {
+        if (e >= r * r) return res[(size_t)(e - r * r) * res_stride];
+        const int a = e / r, b = e - a * r;
+        return (b <= a) ? Sup[(size_t)b * r + a] + R[(size_t)b * ldr + a] : 0.0;
+      },
+      [&](int e, double v) {
+        if (e >= r * r) {
+          A[(size_t)r * ld + e - r * r] = v;
+        } else {
+          const int a = e / r, b = e - a * r;
+          if (b <= a) A[(size_t)a * ld + b] = v;
+        }
+      });
+  __syncthreads();
+  ldl_wave_inv<1, SqLayout, W>(A, SqLayout{ld}, r, r + 1, Dd, true);
+  for (int k = threadIdx.x; k < r; k += blockDim.x) {
+    const double q = sqrt(Dd[k]);
+    sd[k] = q;
+    y_out[k] = A[(size_t)r * ld + k] * q;
+  }
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    double s = 0.0;
+    int ok = 1;
+    for (int k = threadIdx.x; k < r; k += 64) {
+      const double d = Dd[k], v = A[(size_t)r * ld + k] * sd[k];
+      ok &= (isfinite(d) && d > 0.0) ? 1 : 0;
+      s += v * v;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+      s += __shfl_down(s, o, 64);
+      ok &= __shfl_down(ok, o, 64);
+    }
+    if (threadIdx.x == 0) {
+      const int acc = ok && isfinite(s) && !(s > chi2_thr);
+      *gate = acc;
+      gate_out[0] = ok ? s : __builtin_nan("");
+      gate_out[1] = acc;
+    }
+  }
+  for (int e = threadIdx.x; e < r * r; e += blockDim.x) {
+    const int a = e / r, b = e - a * r;
+    double v = 0.0;
+    if (b < a)
+      v = A[(size_t)b * ld + a] / sd[a];
+    else if (b == a)
+      v = 1.0 / sd[a];
+    Linv_out[e] = v;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------
 // K3: tile pair (bi, bj), bi <= bj, of the nb x nb tile grid of P (blocks enumerated row by row)
 __global__ void __launch_bounds__(256) k_ekf_WP(double *__restrict__ P, int ldp, int N, const double *__restrict__ M,
@@ -747,6 +818,54 @@ void launch_ekf_update(hipStream_t s, double *P, int ldp, int N, const double *H
                        const int *hidx, const double *res, int res_stride, double sigma2, EkfScratch &sc) {
   launch_ekf_phaseA(s, P, ldp, N, H, ldh, r, n, hidx, sigma2, sc);
   launch_ekf_phaseB(s, P, ldp, N, r, res, res_stride, sc);
+}
+
+// StateHelper::EKFUpdate (StateHelper.cpp:116-197) with the caller's dense R behind a chi2 gate on its own factor
+// (UpdaterUWB.cpp:67-79): phase A with s2 = 0, k_ekf_fact_R, k_ekf_WP behind the gate int sc.chi2_gate.  As many
+// launches as launch_ekf_update; M, the factor and the P update are that path's kernels.
+void launch_ekf_update_R(hipStream_t s, double *P, int ldp, int N, const double *H, int ldh, int r, int n,
+                         const int *hidx, const double *res, int res_stride, const double *R, int ldr, double chi2_thr,
+                         EkfScratch &sc) {
+  int *gate = sc.chi2_gate;
+  if (!gate) throw std::runtime_error("EKF update with R: no gate in the scratch");
+  if (r + 1 > kWaveMaxRows) throw std::runtime_error("direct EKF update with more rows than the factorization panel");
+  if (ldr < r) throw std::runtime_error("EKF update: leading dimension of R below its row count");
+  if (sc.Tall) throw std::runtime_error("EKF update with R: T of another H in the scratch");
+  launch_ekf_phaseA(s, P, ldp, N, H, ldh, r, n, hidx, 0.0, sc);
+  static bool attrs = false;
+  if (!attrs) {
+    const void *fns[5] = {(const void *)k_ekf_fact_R<1, true>, (const void *)k_ekf_fact_R<2, true>,
+                          (const void *)k_ekf_fact_R<3, true>, (const void *)k_ekf_fact_R<4, true>,
+                          (const void *)k_ekf_fact_R<5, true>};
+    for (int k = 0; k < 5; k++)
+      if (set_dyn_lds(fns[k], kMaxDynLds) < kMaxDynLds)
+        throw std::runtime_error("dynamic LDS limit not granted for k_ekf_fact_R (" + std::to_string(k) + ")");
+    attrs = true;
+  }
+  const size_t bytes = ekf_small_lds_bytes(r);
+  const bool use_lds = bytes <= (size_t)kMaxDynLds;
+  double *Linv = sc.S, *Sup = sc.S + 2 * (size_t)r * r, *Sg = sc.S + 3 * (size_t)r * r;
+  {
+    KScope ks(sc.kp, KC_LDL);
+    const int w = panel_waves(r + 1);
+    auto *kf = use_lds ? (w == 1   ? k_ekf_fact_R<1, true>
+                          : w == 2 ? k_ekf_fact_R<2, true>
+                          : w == 3 ? k_ekf_fact_R<3, true>
+                          : w == 4 ? k_ekf_fact_R<4, true>
+                                   : k_ekf_fact_R<5, true>)
+                       : (w == 1   ? k_ekf_fact_R<1, false>
+                          : w == 2 ? k_ekf_fact_R<2, false>
+                          : w == 3 ? k_ekf_fact_R<3, false>
+                          : w == 4 ? k_ekf_fact_R<4, false>
+                                   : k_ekf_fact_R<5, false>);
+    hipLaunchKernelGGL(kf, dim3(1), dim3(kFactThreads), use_lds ? bytes : 0, s, Sup, r, R, ldr, res, res_stride, Linv,
+                       sc.y, Sg, gate, chi2_thr, sc.dx + N);
+  }
+  if (sc.kp) sc.kp->credit(KC_LDL, (double)r * r * r / 3.0 + (double)r * r, 8.0 * (2.0 * r * r + 2.0 * r));
+  const int nb = (N + 15) / 16;
+  const size_t lw = (size_t)(32 * (r | 1) + 1024) * sizeof(double);
+  hipLaunchKernelGGL(k_ekf_WP, dim3(nb * (nb + 1) / 2), dim3(256), lw, s, P, ldp, N, sc.M, r, sc.S, sc.y, sc.dx, sc.neg,
+                     (const int *)gate, nb);
 }
 
 }  // namespace uvhp

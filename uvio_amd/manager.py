@@ -332,6 +332,40 @@ class VioManager:
                                C.c_double(rng), C.byref(a)), "uwb_update_single")
         return bool(a.value)
 
+    # ---- a measurement of the caller's own: propagate -> read the state -> build H -> update ----
+    def propagate(self, t):
+        """UVioPropagator::propagate: the state to time t (IMU clock) without a clone."""
+        self._check(self._call("propagate", self._h, C.c_double(t)), "propagate")
+
+    def measurement_update(self, blocks, H, res, R, chi2_thr=float("inf")):
+        """StateHelper::EKFUpdate(state, H_order, H, res, R) behind a chi2 gate: blocks = [(covariance id, size), ...]
+        (get_state_vector's meta) name H's column blocks; H is (r, sum sizes) with respect to the error state, R (r, r)
+        with only its upper triangle read.  Returns {"applied", "chi2", "dx"}; dx is zeros when gated."""
+        ids = np.ascontiguousarray([b[0] for b in blocks], dtype=np.int32)
+        sizes = np.ascontiguousarray([b[1] for b in blocks], dtype=np.int32)
+        n = int(sizes.sum()) if len(blocks) else 0
+        res = np.ascontiguousarray(res, dtype=np.float64).reshape(-1)
+        r = res.shape[0]
+        H = np.ascontiguousarray(np.asarray(H, dtype=np.float64).reshape(r, n))
+        R = np.ascontiguousarray(np.asarray(R, dtype=np.float64).reshape(r, r))
+        dx = np.zeros(self.cov_dim())
+        chi2, applied = C.c_double(0.0), C.c_int(0)
+        ip = C.POINTER(C.c_int)
+        self._check(self._call("measurement_update", self._h, len(blocks), ids.ctypes.data_as(ip),
+                               sizes.ctypes.data_as(ip), _dp(H), max(n, 1), r, _dp(res), _dp(R), max(r, 1),
+                               C.c_double(chi2_thr), C.byref(chi2), C.byref(applied), _dp(dx)), "measurement_update")
+        return {"applied": bool(applied.value), "chi2": chi2.value, "dx": dx}
+
+    def position_fix(self, p_meas, p_SinI, R, chi2_mult=1.0):
+        """A position sensor S rigidly mounted at p_SinI (IMU frame) that measures its own position in the global
+        frame: h(x) = p_IinG + R_GtoI^T p_SinI, linearized at the current values (position_fix_jacobian), gated at
+        chi2_mult * chi2_95(3)."""
+        x = self.get_imu_state()[1]
+        pred, H = position_fix_jacobian(x[0:4], x[4:7], p_SinI)
+        imu = [m for m in self.get_state_vector()[1] if m[0] == 0][0]  # kind 0: the IMU; its pose is columns 0 .. 5
+        return self.measurement_update([(int(imu[1]), 6)], H, np.asarray(p_meas, dtype=np.float64) - pred, R,
+                                       chi2_mult * chi2_95(3))
+
     # ---- getters ----
     def initialized(self):
         """VioManager::initialized (VioManager.h:99): initialize_with_gt ran or an initializer succeeded."""
@@ -657,6 +691,52 @@ def ekf_update(P, H_index, H, res, sigma2, compressed=False):
     rc = fn(_dp(P), Nn, idx.ctypes.data_as(C.POINTER(C.c_int)), n, _dp(H), r, _dp(res), float(sigma2), _dp(dx))
     N.check(rc, what="uvio_hp_ekf_update")
     return P, dx
+
+
+def ekf_update_R(P, H_index, H, res, R, chi2_thr=float("inf"), ldr=None):
+    """StateHelper::EKFUpdate with a dense R (upper triangle read) behind a chi2 gate, on a standalone covariance, on
+    the device.  Returns (P_new, dx, chi2, applied); not applied: P unchanged, dx zeros."""
+    lib = N.load()
+    P = np.array(P, dtype=np.float64, order="C", copy=True)
+    H = np.ascontiguousarray(H, dtype=np.float64)
+    res = np.ascontiguousarray(res, dtype=np.float64)
+    R = np.ascontiguousarray(R, dtype=np.float64)
+    idx = np.ascontiguousarray(H_index, dtype=np.int32)
+    Nn = P.shape[0]
+    r, n = H.shape
+    dx = np.zeros(Nn)
+    chi2, applied = C.c_double(0.0), C.c_int(0)
+    rc = lib.uvio_hp_ekf_update_r(_dp(P), Nn, idx.ctypes.data_as(C.POINTER(C.c_int)), n, _dp(H), r, _dp(res), _dp(R),
+                                  R.shape[1] if ldr is None else int(ldr), float(chi2_thr), _dp(dx), C.byref(chi2),
+                                  C.byref(applied))
+    if rc != 0:
+        msg = (lib.uvio_hp_last_error(None) or b"").decode() if rc == N.E_ARG else ""
+        raise RuntimeError("uvio_hp_ekf_update_r failed: %s %s" % (N.ERRNAMES.get(rc, rc), msg))
+    return P, dx, chi2.value, bool(applied.value)
+
+
+def chi2_95(dof):
+    """The 95 % chi-squared quantile the reference's updaters multiply their chi2_multipler into (dof 1 .. 999)."""
+    out = C.c_double(0.0)
+    N.check(N.load().uvio_hp_chi2_95(int(dof), C.byref(out)), what="uvio_hp_chi2_95")
+    return out.value
+
+
+def quat_2_Rot(q):
+    """JPL quaternion (x, y, z, w) -> rotation matrix (ov_core quat_ops.h quat_2_Rot)."""
+    q = np.asarray(q, dtype=np.float64)
+    x, y, z, w = q
+    S = np.array([[0.0, -z, y], [z, 0.0, -x], [-y, x, 0.0]])
+    return (2.0 * w * w - 1.0) * np.eye(3) - 2.0 * w * S + 2.0 * np.outer(q[:3], q[:3])
+
+
+def position_fix_jacobian(q_GtoI, p_IinG, p_SinI):
+    """h(x) = p_IinG + R_GtoI^T p_SinI and its (3, 6) Jacobian over the IMU pose's error state [dtheta, dp] (JPL left
+    error, R(dtheta (x) q) ~ (I - [dtheta]x) R): H_theta = -R_GtoI^T [p_SinI]x, H_p = I.  Returns (h, H)."""
+    Rm = quat_2_Rot(q_GtoI)
+    s = np.asarray(p_SinI, dtype=np.float64)
+    S = np.array([[0.0, -s[2], s[1]], [s[2], 0.0, -s[0]], [-s[1], s[0], 0.0]])
+    return np.asarray(p_IinG, dtype=np.float64) + Rm.T @ s, np.hstack([-Rm.T @ S, np.eye(3)])
 
 
 def compress(A):
