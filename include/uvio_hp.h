@@ -385,7 +385,12 @@ typedef struct {
 int uvio_hp_set_state(uvio_hp_t *h, const double *val, const double *fej, int len, const double *P, int N, int ld);
 /* Propagator::propagate_and_clone (Propagator.h:110) to t with the IMU readings fed so far */
 int uvio_hp_propagate_and_clone(uvio_hp_t *h, double t);
-/* UpdaterMSCKF::update (UpdaterMSCKF.h:68, UpdaterMSCKF.cpp:58-295) */
+/* UpdaterMSCKF::update (UpdaterMSCKF.h:68, UpdaterMSCKF.cpp:58-295).
+ * UVIO_HP_E_CAPACITY, before the batch's kernels (covariance and state untouched, the handle stays usable): a feature of
+ * more than 64 measurements; a batch whose largest measurement count and widest per-feature Jacobian, taken
+ * together, need more LDS than the feature kernel has (e.g. 60 measurements of a feature over 30 clones of a
+ * calibrated stereo pair, or a 64-measurement feature in one batch with a feature over 25 clones); 512 or more
+ * state columns in one batch.  uvio_hp_slam_update's batches pass the same check. */
 int uvio_hp_msckf_update(uvio_hp_t *h, int nfeat, const uint64_t *featids, const int *meas_off,
                          const uvio_hp_feat_meas_t *meas, uvio_hp_feat_result_t *out);
 /* UpdaterSLAM::update (UpdaterSLAM.h:70, UpdaterSLAM.cpp:253-479); every feature must be a SLAM landmark of
@@ -469,6 +474,11 @@ int uvio_hp_shard_partition(const int *rows, int n, int world, int *bounds);
 /* per-feature results of the last UpdaterMSCKF::update: feature id, triangulated p_FinG (3 per
  * feature), status (0 accepted, 1 triangulation/refinement failed, 3 chi2 rejected) and chi2 */
 int uvio_hp_debug_last_msckf(uvio_hp_t *h, uint64_t *ids, double *pG, int *status, double *chi2, int cap, int *n);
+/* the correction dx = K res of the last UpdaterMSCKF::update, indexed by covariance id (*n = its length, the
+ * covariance dimension at that update; zeros when no feature was accepted; *n = 0 before the first update).  The
+ * update reads dx back anyway; this is what a test compares in units of the prior standard deviations, which the
+ * updated state, stored in double precision, cannot show.  UVIO_HP_E_CAPACITY when cap < *n. */
+int uvio_hp_debug_last_msckf_dx(uvio_hp_t *h, double *dx, int cap, int *n);
 /* per-feature results of every updater call of the last camera frame, in call order: kind (0
  * UpdaterMSCKF::update, 1 UpdaterSLAM::update, 2 UpdaterSLAM::delayed_init), feature id, p_FinG (MSCKF:
  * triangulated; delayed init: triangulated before the landmark's initialization; SLAM update: 0),

@@ -394,12 +394,21 @@ int uvio_hp_debug_last_msckf(uvio_hp_t *h, uint64_t *ids, double *pG, int *statu
     if (k < cap) {
       ids[k] = d.id;
       for (int j = 0; j < 3; j++) pG[3 * k + j] = d.p_FinG[j];
-      status[k] = d.status;
+      status[k] = Engine::debug_status(d.status);
       chi2[k] = d.chi2;
     }
     k++;
   }
   *n = k;
+  return 0;
+}
+
+int uvio_hp_debug_last_msckf_dx(uvio_hp_t *h, double *dx, int cap, int *n) {
+  if (!h || !n) return UVIO_HP_E_ARG;
+  const auto &v = h->e->last_msckf_dx_;
+  *n = (int)v.size();
+  if ((int)v.size() > cap || (!dx && !v.empty())) return UVIO_HP_E_CAPACITY;
+  std::copy(v.begin(), v.end(), dx);
   return 0;
 }
 
@@ -412,7 +421,7 @@ int uvio_hp_debug_frame_feats(uvio_hp_t *h, int *kind, uint64_t *ids, double *pG
       kind[k] = kd.first;
       ids[k] = kd.second.id;
       for (int j = 0; j < 3; j++) pG[3 * k + j] = kd.second.p_FinG[j];
-      status[k] = kd.second.status;
+      status[k] = Engine::debug_status(kd.second.status);
       chi2[k] = kd.second.chi2;
     }
     k++;

@@ -625,7 +625,12 @@ class Engine {
     int status;
     double chi2;
   };
+  // status is the feature kernel's own (2 = refinement failed, which uvio_hp_feat_result_t reports); the debug
+  // getters fold it into 1, as the reference's debug output has it (debug_status)
+  static int debug_status(int status) { return status == 2 ? 1 : status; }
   std::vector<FeatDebug> last_msckf_;
+  // dx of the last UpdaterMSCKF::update (N doubles; zeros when no feature was accepted): uvio_hp_debug_last_msckf_dx
+  std::vector<double> last_msckf_dx_;
   std::vector<FeatDebug> last_upd_;  // the last SLAM update / delayed initialization, per feature
   // every updater's per-feature results of the current frame: (kind 0 MSCKF / 1 SLAM update / 2 delayed
   // initialization, result), cleared when the frame's update stage begins (lock-step parity tests)

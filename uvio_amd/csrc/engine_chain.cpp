@@ -81,6 +81,7 @@ int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, s
                          size_t slam_chunk, const char *stage_name) {
   stage_ = stage_name;
   last_msckf_.clear();
+  last_msckf_dx_.clear();
   last_upd_.clear();
   std::vector<double> clonetimes;
   for (auto &c : clones_) clonetimes.push_back(c.first);
@@ -296,6 +297,24 @@ int Engine::update_frame(std::vector<FeatP> &up, std::vector<FeatP> &slam_upd, s
       max_nf = std::max(max_nf, F.nf);
     }
     if (max_meas > kMaxMeasPerFeat) throw HpError(UVIO_HP_E_CAPACITY, "too many measurements per feature");
+    // what the launch wrappers below would refuse with std::runtime_error (an internal error, fatal for the handle)
+    // is an ordinary caller-built input: refused here, before any of the batch's kernels (its tables may be staged
+    // and a prefactor of its columns in flight on the side stream already; covariance and state are untouched)
+    if (b.n_canon >= kMaxCanonCols)
+      throw HpError(UVIO_HP_E_CAPACITY, "update batch over " + std::to_string(b.n_canon) + " state columns, the feature kernel takes " +
+                                            std::to_string(kMaxCanonCols - 1));
+    if (feature_lds_bytes(max_meas, max_nf) > feature_lds_limit())
+      throw HpError(UVIO_HP_E_CAPACITY, "a feature of " + std::to_string(max_meas) + " measurements beside one of " +
+                                            std::to_string(max_nf) + " Jacobian columns needs " +
+                                            std::to_string(feature_lds_bytes(max_meas, max_nf)) +
+                                            " B of the feature kernel's LDS, the limit is " +
+                                            std::to_string(feature_lds_limit()));
+    if (chi2) {
+      int max_rows_f = 0;
+      for (auto &F : b.feats) max_rows_f = std::max(max_rows_f, (mode == 0) ? 2 * F.nmeas - 3 : 2 * F.nmeas);
+      const std::string why = chi2_batch_refusal(max_rows_f, b.n_canon, mode == 1);
+      if (!why.empty()) throw HpError(UVIO_HP_E_CAPACITY, why);
+    }
     b.fout_off = fo;
     fo += nf;
     if (!it.staged) {
@@ -660,7 +679,7 @@ void Engine::replay_msckf(ChainItem &it) {
   int acc = 0, acc_rows = 0;
   for (size_t i = 0; i < outs.size(); i++) {
     last_msckf_.push_back(FeatDebug{it.fv[i]->featid, {outs[i].p_FinG[0], outs[i].p_FinG[1], outs[i].p_FinG[2]},
-                                    outs[i].status == 2 ? 1 : outs[i].status, outs[i].chi2});
+                                    outs[i].status, outs[i].chi2});
     frame_feats_.push_back({0, last_msckf_.back()});
     it.fv[i]->to_delete = true;
     for (int k = 0; k < 3; k++) it.fv[i]->p_FinG[k] = outs[i].p_FinG[k], it.fv[i]->p_FinA[k] = outs[i].p_FinA[k];
@@ -668,6 +687,7 @@ void Engine::replay_msckf(ChainItem &it) {
   }
   timing_.msckf_rows = acc_rows;
   timing_.msckf_cols = it.b.n_canon;
+  last_msckf_dx_.assign((size_t)N_, 0.0);
   if (it.region < 0) return;
   const double *base = d_.region_host(it.region);
   neg_check(base, N_);
@@ -675,7 +695,10 @@ void Engine::replay_msckf(ChainItem &it) {
     acc = base[N_ + 8] > 0.5 ? 1 : 0;
     timing_.msckf_rows = (int)(base[N_ + 11] + 0.5);
   }
-  if (acc > 0) apply_dx(base);
+  if (acc > 0) {
+    last_msckf_dx_.assign(base, base + N_);
+    apply_dx(base);
+  }
 }
 
 // one UpdaterSLAM::update chunk

@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 
 #include "dev_mem.h"
 #include "hp_math.h"
@@ -170,6 +171,12 @@ void launch_chi2_batch(hipStream_t s, const DBatchParams &bp, const DFeat *feats
                        double *H_all, int m, double *T_all, const double *chi2_table, DFeatOut *out, int max_rows_f,
                        int *acc_count, double *pcan, DevBuf<double> &sbuf, bool small_gate);
 size_t feature_lds_bytes(int max_meas, int max_nf);
+// What a batch may ask of the two launches above, for a caller that refuses before it enqueues anything: the dynamic
+// LDS k_feature may use (feature_lds_bytes of the batch's max_meas and max_nf has to fit; n_canon < kMaxCanonCols
+// besides), and the reason launch_chi2_batch would refuse a batch of this shape (empty: it runs)
+constexpr int kMaxCanonCols = 512;  // k_feature's canon2loc table
+size_t feature_lds_limit();
+std::string chi2_batch_refusal(int max_rows_f, int n, bool small_gate);
 
 // Compression: G = A^T A over rows of A = H_all (m x (n+1), ld = ldh), partials then Cholesky ->
 // R_aug ((n+1) x (n+1) upper, ld = ldr).  Rank-deficient pivots produce zero rows.

@@ -577,17 +577,71 @@ static size_t chi2_small_lds_bytes(int n) {
          (size_t)n * sizeof(int);
 }
 
+// The dynamic LDS each gate kernel may use: what set_dyn_lds granted it (asked once), and the 64 KB every kernel has
+// without asking.  launch_chi2_batch and chi2_batch_refusal decide from the same numbers.
+static size_t lds_limit(int &granted, const void *fn) {
+  if (granted < 0) granted = set_dyn_lds(fn, kMaxDynLds);
+  return (size_t)std::max(granted, 64 * 1024);
+}
+static size_t chi2_small_lds_limit() {
+  static int granted = -1;
+  return lds_limit(granted, (const void *)k_chi2_small);
+}
+typedef void (*Chi2Fn)(DBatchParams, const DFeat *, double *, double *, const double *, DFeatOut *, int, int *,
+                       const double *, size_t);
+static const Chi2Fn kChi2Fn[4] = {k_chi2<1>, k_chi2<2>, k_chi2<3>, k_chi2<4>};
+static int chi2_instance(int max_rows_f) { return std::min(std::max((max_rows_f + 1 + 63) / 64, 1), 4) - 1; }
+static size_t chi2_lds_limit(int inst) {
+  static int granted[4] = {-1, -1, -1, -1};
+  return lds_limit(granted[inst], (const void *)kChi2Fn[inst]);
+}
+static size_t chi2_S2_lds_limit() {
+  static int granted = -1;
+  return lds_limit(granted, (const void *)k_chi2_S2);
+}
+// k_chi2's own LDS: H, T and S of the largest feature, or S and the solve's vectors alone when S comes from global
+// memory (chi2_lds_bytes beyond kMaxDynLds)
+static size_t chi2_kernel_lds_bytes(int max_rows_f, int n) {
+  const size_t bytes = chi2_lds_bytes(max_rows_f, n);
+  if (bytes <= (size_t)kMaxDynLds) return bytes;
+  return ((size_t)(max_rows_f + 1) * (max_rows_f | 1) + 4 * (size_t)(max_rows_f + 1)) * sizeof(double);
+}
+static size_t chi2_S2_lds_bytes(int max_rows_f) {
+  const int nt = (max_rows_f + 15) / 16;
+  return (size_t)2 * 16 * nt * (kS2KC + 1) * sizeof(double);
+}
+
+std::string chi2_batch_refusal(int max_rows_f, int n, bool small_gate) {
+  auto over = [](const char *what, size_t need, size_t limit) {
+    return std::string(what) + " needs " + std::to_string(need) + " B of LDS, the limit is " + std::to_string(limit);
+  };
+  if (small_gate && max_rows_f <= kGateMaxRows && !(slam_seven_parts() & kSevenGate)) {
+    const size_t bytes = chi2_small_lds_bytes(n);
+    return bytes > chi2_small_lds_limit() ? over("the small chi2 gate", bytes, chi2_small_lds_limit()) : std::string();
+  }
+  if (max_rows_f + 1 > kWaveMaxRows)
+    return "a feature of " + std::to_string(max_rows_f) + " rows is wider than the chi2 factorization panel (" +
+           std::to_string(kWaveMaxRows - 1) + ")";
+  const int inst = chi2_instance(max_rows_f);
+  const size_t bytes = chi2_kernel_lds_bytes(max_rows_f, n);
+  if (bytes > chi2_lds_limit(inst)) return over("the chi2 gate", bytes, chi2_lds_limit(inst));
+  const int nt = (max_rows_f + 15) / 16;
+  if (chi2_lds_bytes(max_rows_f, n) > (size_t)kMaxDynLds && nt * (nt + 1) / 2 <= kS2Waves * kS2Tiles &&
+      chi2_S2_lds_bytes(max_rows_f) > chi2_S2_lds_limit())
+    return over("the chi2 gate's S kernel", chi2_S2_lds_bytes(max_rows_f), chi2_S2_lds_limit());
+  return std::string();
+}
+
 void launch_chi2_batch(hipStream_t s, const DBatchParams &bp, const DFeat *feats, const double *P, const int *hidx,
                        double *H_all, int m, double *T_all, const double *chi2_table, DFeatOut *out, int max_rows_f,
                        int *acc_count, double *pcan, DevBuf<double> &sbuf, bool small_gate) {
   if (bp.nfeat <= 0 || m <= 0) return;
   const int n = bp.n_canon;
   if (small_gate && max_rows_f <= kGateMaxRows && !(slam_seven_parts() & kSevenGate)) {
-    static int granted = -1;
-    if (granted < 0) granted = set_dyn_lds((const void *)k_chi2_small, kMaxDynLds);
     const size_t bytes = chi2_small_lds_bytes(n);
-    if (bytes > 64 * 1024 && (int)bytes > granted)
-      throw std::runtime_error("k_chi2_small needs " + std::to_string(bytes) + " B of LDS, granted " + std::to_string(granted));
+    if (bytes > chi2_small_lds_limit())
+      throw std::runtime_error("k_chi2_small needs " + std::to_string(bytes) + " B of LDS, granted " +
+                               std::to_string(chi2_small_lds_limit()));
     const int waves = std::min(16, std::max(2, (n + 15) / 16));  // a wave per column tile of T; ldl_wave_inv needs >= 2
     hipLaunchKernelGGL(k_chi2_small, dim3(bp.nfeat), dim3(64 * waves), bytes, s, bp, feats, P, hidx, H_all, T_all,
                        chi2_table, out, acc_count);
@@ -608,20 +662,14 @@ void launch_chi2_batch(hipStream_t s, const DBatchParams &bp, const DFeat *feats
                        sizeof(int) * (size_t)n, s, H_all, m, n, bp.ldh, P, bp.ldp, hidx, T_all, bp.ldh, acc_count);
   if (max_rows_f + 1 > kWaveMaxRows)
     throw std::runtime_error("feature with " + std::to_string(max_rows_f) + " rows: wider than the chi2 factorization panel");
-  size_t bytes = chi2_lds_bytes(max_rows_f, n);
-  int use_lds = bytes <= kMaxDynLds;
-  if (!use_lds) bytes = ((size_t)(max_rows_f + 1) * (max_rows_f | 1) + 4 * (size_t)(max_rows_f + 1)) * sizeof(double);
+  int use_lds = chi2_lds_bytes(max_rows_f, n) <= kMaxDynLds;
+  const size_t bytes = chi2_kernel_lds_bytes(max_rows_f, n);
   // the instance for the batch's largest feature (R + 1 rows with the residual row)
-  const int smax = (max_rows_f + 1 + 63) / 64;
-  typedef void (*Chi2Fn)(DBatchParams, const DFeat *, double *, double *, const double *, DFeatOut *, int, int *,
-                         const double *, size_t);
-  static const Chi2Fn kChi2Fn[4] = {k_chi2<1>, k_chi2<2>, k_chi2<3>, k_chi2<4>};
-  const Chi2Fn chi2_fn = kChi2Fn[std::min(std::max(smax, 1), 4) - 1];
-  static int granted_inst[4] = {-1, -1, -1, -1};
-  int &granted = granted_inst[std::min(std::max(smax, 1), 4) - 1];
-  if (granted < 0) granted = set_dyn_lds((const void *)chi2_fn, kMaxDynLds);
-  if (bytes > 64 * 1024 && (int)bytes > granted)
-    throw std::runtime_error("k_chi2 needs " + std::to_string(bytes) + " B of LDS, granted " + std::to_string(granted));
+  const int inst = chi2_instance(max_rows_f);
+  const Chi2Fn chi2_fn = kChi2Fn[inst];
+  if (bytes > chi2_lds_limit(inst))
+    throw std::runtime_error("k_chi2 needs " + std::to_string(bytes) + " B of LDS, granted " +
+                             std::to_string(chi2_lds_limit(inst)));
   // features too large for the LDS staging: S over many CUs first (k_chi2_S2 / k_chi2_S), k_chi2 reads it
   double *Sg = nullptr;
   size_t stride = 0;
@@ -635,12 +683,11 @@ void launch_chi2_batch(hipStream_t s, const DBatchParams &bp, const DFeat *feats
     }
     Sg = sbuf;
     const int nt = (max_rows_f + 15) / 16, groups = (nt * (nt + 1) / 2 + kChiSWaves - 1) / kChiSWaves;
-    const size_t s2_bytes = (size_t)2 * 16 * nt * (kS2KC + 1) * sizeof(double);
+    const size_t s2_bytes = chi2_S2_lds_bytes(max_rows_f);
     if (nt * (nt + 1) / 2 <= kS2Waves * kS2Tiles) {
-      static int granted2 = -1;
-      if (granted2 < 0) granted2 = set_dyn_lds((const void *)k_chi2_S2, kMaxDynLds);
-      if (s2_bytes > 64 * 1024 && (int)s2_bytes > granted2)
-        throw std::runtime_error("k_chi2_S2 needs " + std::to_string(s2_bytes) + " B of LDS, granted " + std::to_string(granted2));
+      if (s2_bytes > chi2_S2_lds_limit())
+        throw std::runtime_error("k_chi2_S2 needs " + std::to_string(s2_bytes) + " B of LDS, granted " +
+                                 std::to_string(chi2_S2_lds_limit()));
       hipLaunchKernelGGL(k_chi2_S2, dim3(bp.nfeat), dim3(kS2Threads), s2_bytes, s, bp, feats, H_all, T_all, out, Sg,
                          stride);
     } else {

@@ -927,6 +927,12 @@ __global__ void __launch_bounds__(256) k_feature(DBatchParams bp, const DFeat *_
 #undef FEAT_TS
 }
 
+size_t feature_lds_limit() {
+  static int granted = -1;
+  if (granted < 0) granted = set_dyn_lds((const void *)k_feature, 156 * 1024);
+  return (size_t)std::max(granted, 64 * 1024);
+}
+
 void launch_feature_linearize(hipStream_t s, const DBatchParams &bp, const DFeat *feats, const DMeas *meas,
                               const DVar *vars, const DClone *clones, const DCam *cams, const double *P,
                               const double *chi2_table, double *H_all, DFeatOut *out, int max_meas, int max_nf,
@@ -936,10 +942,9 @@ void launch_feature_linearize(hipStream_t s, const DBatchParams &bp, const DFeat
     throw std::runtime_error("k_feature: n_canon " + std::to_string(bp.n_canon) + " / measurements per feature " +
                              std::to_string(max_meas) + " beyond the kernel's limits (511 / 64)");
   size_t bytes = feature_lds_bytes(max_meas, max_nf);
-  static int granted = -1;
-  if (granted < 0) granted = set_dyn_lds((const void *)k_feature, 156 * 1024);
-  if (bytes > 64 * 1024 && (int)bytes > granted)
-    throw std::runtime_error("k_feature needs " + std::to_string(bytes) + " B of LDS, granted " + std::to_string(granted));
+  if (bytes > feature_lds_limit())
+    throw std::runtime_error("k_feature needs " + std::to_string(bytes) + " B of LDS, granted " +
+                             std::to_string(feature_lds_limit()));
   hipLaunchKernelGGL(k_feature, dim3(bp.nfeat), dim3(256), bytes, s, bp, feats, meas, vars, clones, cams, P,
                      chi2_table, H_all, out, max_meas, max_nf, zero);
 }

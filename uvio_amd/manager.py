@@ -440,6 +440,13 @@ class VioManager:
         k = n.value
         return ids[:k].copy(), pG[:k].copy(), st[:k].copy(), c2[:k].copy()
 
+    def debug_last_msckf_dx(self):
+        """dx of the last UpdaterMSCKF::update, indexed by covariance id (zeros when nothing was accepted)"""
+        dx = np.zeros(4096)
+        n = C.c_int()
+        self._check(self._call("debug_last_msckf_dx", self._h, _dp(dx), dx.size, C.byref(n)), "debug_last_msckf_dx")
+        return dx[:n.value].copy()
+
     def debug_frame_feats(self):
         """Per-feature results of every updater call of the last frame: (kind, ids, p_FinG, status, chi2);
         kind 0 MSCKF update, 1 SLAM update, 2 delayed initialization."""
