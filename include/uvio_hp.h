@@ -42,6 +42,7 @@ extern "C" {
 
 #define UVIO_HP_MAX_CAMS 4
 #define UVIO_HP_MAX_ANCHORS 16
+#define UVIO_HP_AUX_MAX_DIM 8 /* scalars of one caller-defined state variable (uvio_hp_aux_add) */
 
 /* ---- option structs: the keys of estimator_config.yaml / kalibr_*.yaml / uwb_*.yaml ---- */
 
@@ -140,6 +141,10 @@ typedef struct {
    * disparity threshold; init_dyn_use selects the dynamic initializer, which is not built */
   double init_window_time, init_imu_thresh, init_max_disparity;
   int init_dyn_use;
+  /* capacity reserved for caller-defined ("auxiliary") state variables (uvio_hp_aux_add): the sum of their
+   * dimensions the covariance has room for.  0 (the default): none, and every buffer has the size it has without
+   * the option.  Not a reference key; uvio_hp_options_load reads "max_aux_dim" if the file has it */
+  int max_aux_dim;
 } uvio_hp_options_t;
 
 /* Per-frame stage timings in seconds, the reference CSV schema
@@ -442,11 +447,52 @@ int uvio_hp_propagate(uvio_hp_t *h, double t);
  * positive number; uvio_hp_last_error says so); covariance and mean are untouched and the handle stays usable.
  * UVIO_HP_E_NUMERIC (fatal, as everywhere): a negative covariance diagonal after an accepted update.
  * Serialized with the feeds.  When applied the odometry cache is republished, as after uvio_hp_msckf_update.
- * Not covered: state variables of the caller's own (a sensor bias or lever arm), buffering such measurements
- * inside uvio_hp_feed_camera as UWB messages are, and chains of relinearized updates on the device. */
+ * A state variable of the caller's own (a sensor bias, a lever arm) is added with uvio_hp_aux_add below and named
+ * here like any other block.  Not covered: buffering such measurements inside uvio_hp_feed_camera as UWB messages
+ * are, and chains of relinearized updates on the device. */
 int uvio_hp_measurement_update(uvio_hp_t *h, int nvar, const int *ids, const int *sizes, const double *H, int ldh, int r,
                                const double *res, const double *R, int ldr, double chi2_thr, double *chi2, int *applied,
                                double *dx);
+
+/* ---- state variables of the caller's own ("auxiliary" states: a lever arm, a sensor bias, a frame offset, a scale) ----
+ * Small additive vectors (1 .. UVIO_HP_AUX_MAX_DIM scalars, updated as value += dx like ov_type::Vec) appended to
+ * the running estimator the way uvio appends p_IinU and its anchors (StateHelper::set_initial_covariance,
+ * StateHelper.cpp:199-223; StateHelper::initialize_invertible, StateHelper.cpp:484-577), but on the device: the new
+ * rows and columns of the covariance are written in place, nothing is copied to the host.  The options' max_aux_dim
+ * reserves the room.  A variable shows in uvio_hp_get_state_vector's meta as kind 6 and is named in
+ * uvio_hp_measurement_update / uvio_hp_get_marginal_cov by its covariance offset, which MOVES when clones or
+ * landmarks in front of it are marginalized: ask uvio_hp_aux_get for the offset before building an H.  The handle
+ * (a positive int) stays valid until uvio_hp_aux_remove.  With feature sharding every rank must add the same
+ * variables at the same points of the stream.
+ * Refusals come before any device work and leave the state and the covariance untouched: UVIO_HP_E_STATE before
+ * initialization; UVIO_HP_E_ARG for a null pointer, dim outside 1 .. 8, a block outside [0, N), a leading dimension
+ * below the row length, a non-finite input, a prior diagonal that is not positive, a negative walk_sigma, a singular
+ * H_aux, a dead handle; UVIO_HP_E_CAPACITY when the live aux dimensions plus dim exceed max_aux_dim, or H_x has more
+ * than 1215 columns.  Serialized with the feeds. */
+/* A variable with value val[dim] and the prior covariance prior_cov (dim x dim, leading dimension ld; only the upper
+ * triangle is read, as for R), uncorrelated with everything else.  walk_sigma[dim] (NULL: all zero, a constant) is
+ * the continuous-time random-walk density of each component in unit / sqrt(s): wherever the state time advances by
+ * dt (a camera frame's propagation, uvio_hp_propagate, a UWB message, a zero-velocity update) the component's
+ * variance grows by walk_sigma^2 * dt. */
+int uvio_hp_aux_add(uvio_hp_t *h, int dim, const double *val, const double *prior_cov, int ld, const double *walk_sigma,
+                    int *handle);
+/* StateHelper::initialize_invertible for a caller's variable: dim rows of a measurement
+ * res = H_x dx + H_aux dx_aux + noise(R) with H_x (dim x n, leading dimension ldhx) over the blocks
+ * [ids[k], ids[k] + sizes[k]) as in uvio_hp_measurement_update (nvar may be 0), an invertible H_aux (dim x dim,
+ * ldha) and a dense R (dim x dim, ldr, upper triangle read).  The value becomes val0 + H_aux^-1 res, the
+ * cross-covariance -P[:, I] H_x^T H_aux^-T and the variable's own block H_aux^-1 (H_x P_II H_x^T + R) H_aux^-T.
+ * H_aux^-1 is formed on the host (Gauss-Jordan, partial pivoting; a pivot not above dim * 2^-52 * max |H_aux| is
+ * singular). */
+int uvio_hp_aux_add_from_measurement(uvio_hp_t *h, int dim, const double *val0, int nvar, const int *ids,
+                                     const int *sizes, const double *H_x, int ldhx, const double *H_aux, int ldha,
+                                     const double *res, const double *R, int ldr, const double *walk_sigma,
+                                     int *handle);
+/* the variable's current covariance offset, its dimension and its value (val: dim doubles, may be NULL) */
+int uvio_hp_aux_get(uvio_hp_t *h, int handle, int *id, int *dim, double *val);
+/* StateHelper::marginalize of the variable; the handle is dead afterwards */
+int uvio_hp_aux_remove(uvio_hp_t *h, int handle);
+/* number of live aux variables and the sum of their dimensions (either pointer may be NULL) */
+int uvio_hp_aux_count(uvio_hp_t *h, int *n, int *dims_used);
 
 /* ---- feature-sharded MSCKF update across GPUs (BASELINE.json configs 4-5) ----
  * One process per GPU, each with its own handle fed the same measurement stream (the filter state is
@@ -505,6 +551,23 @@ int uvio_hp_ekf_update(double *P, int N, const int *H_index, int n, const double
  * S that is not positive definite (uvio_hp_last_error(NULL) says so). */
 int uvio_hp_ekf_update_r(double *P, int N, const int *H_index, int n, const double *H, int r, const double *res,
                          const double *R, int ldr, double chi2_thr, double *dx_out, double *chi2, int *applied);
+/* The three kernels of the uvio_hp_aux_* calls on a caller's host covariance, at shapes a test chooses.  P holds
+ * at least N + dim (append, init) or N (walk) rows of ld doubles, ld >= that row count; the rows are uploaded with
+ * their padding, the kernel runs at leading dimension ld, and the rows come back.
+ * _append_p: rows / columns N .. N + dim - 1 <- zeros against [0, N), the prior (dim x dim, ldp, upper triangle
+ * read, finite, positive diagonal) mirrored into the block.
+ * _init_p: rows / columns N .. N + dim - 1 as uvio_hp_aux_add_from_measurement writes them, H_x (dim x n, ldhx) over
+ * the columns H_index (n <= 1215, any order) and H_auxinv = H_aux^-1 (dim x dim, packed) given; res is not read
+ * (it only moves the value) and may be NULL.
+ * _walk_p: P[i][i] += sigma2 * dt for every component of the ntab blocks [ids[t], ids[t] + dims[t]) (disjoint,
+ * dims 1 .. 8; sigma2: the blocks' components concatenated, finite, >= 0; dt finite, >= 0), the product rounded,
+ * then the sum.
+ * UVIO_HP_E_ARG / UVIO_HP_E_CAPACITY before any device work as for the handle's calls. */
+int uvio_hp_aux_append_p(double *P, int N, int ld, int dim, const double *prior, int ldp);
+int uvio_hp_aux_init_p(double *P, int N, int ld, int dim, const int *H_index, int n, const double *H_x, int ldhx,
+                       const double *H_auxinv, const double *res_unused_or_null, const double *R, int ldr);
+int uvio_hp_aux_walk_p(double *P, int N, int ld, int ntab, const int *ids, const int *dims, const double *sigma2,
+                       double dt);
 /* boost::math::quantile(chi_squared(dof), 0.95), the table every reference updater multiplies its chi2_multipler
  * into (UpdaterMSCKF.cpp:52-55, UpdaterSLAM.cpp:55-58, UpdaterZeroVelocity.cpp:59-62, UpdaterUWB.h:33-36), for
  * dof 1 .. 999; UVIO_HP_E_ARG outside that range. */

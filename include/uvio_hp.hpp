@@ -14,6 +14,8 @@
  *   Manager::propagate_and_clone   <- Propagator::propagate_and_clone (Propagator.h:110)
  *   Manager::propagate             <- UVioPropagator::propagate (UVioPropagator.cpp:27)
  *   Manager::measurement_update    <- StateHelper::EKFUpdate (StateHelper.h:88) behind UpdaterUWB.cpp:67-79's gate
+ *   Manager::add_state             <- StateHelper::set_initial_covariance (StateHelper.cpp:199) for a variable of the caller's
+ *   Manager::add_state_from_measurement <- StateHelper::initialize_invertible (StateHelper.cpp:484)
  */
 #ifndef UVIO_HP_HPP
 #define UVIO_HP_HPP
@@ -73,6 +75,20 @@ inline void position_fix_jacobian(const double imu[7], const std::array<double, 
       H[6 * i + j] = -a;
       H[6 * i + 3 + j] = i == j ? 1.0 : 0.0;
     }
+  }
+}
+
+// position_fix_jacobian with the lever arm a state variable of the caller's (Manager::add_state): the antenna A at
+// p_AinI measures z = p_IinG + R_ItoG p_AinI (R_ItoG = R_GtoI^T).  H (3 x 9, row-major) over [dtheta, dp, dp_AinI]:
+// [-R_ItoG [p_AinI]x, I, R_ItoG]; h (3) is the prediction.
+inline void position_fix_lever_arm_jacobian(const double imu[7], const std::array<double, 3> &p_AinI, double h[3],
+                                            double H[27]) {
+  double H6[18];
+  position_fix_jacobian(imu, p_AinI, h, H6);
+  const std::array<double, 9> R = quat_2_Rot(imu);
+  for (int i = 0; i < 3; i++) {
+    for (int j = 0; j < 6; j++) H[9 * i + j] = H6[6 * i + j];
+    for (int j = 0; j < 3; j++) H[9 * i + 6 + j] = R[(size_t)(3 * j + i)];
   }
 }
 
@@ -381,6 +397,75 @@ class Manager {
     for (const auto &m : state_meta())
       if (m[0] == 0) imu_id = m[1];  // kind 0: the IMU; its pose is its first 6 columns
     return measurement_update({{imu_id, 6}}, std::vector<double>(H, H + 18),
+                              {p_meas[0] - h[0], p_meas[1] - h[1], p_meas[2] - h[2]},
+                              std::vector<double>(R.begin(), R.end()), chi2_mult * chi2_95(3));
+  }
+
+  // ---- state variables of the caller's own (uvio_hp_aux_*): a lever arm, a sensor bias, a frame offset, a scale ----
+  // A new additive variable of val.size() scalars (1 .. 8) with the prior covariance prior_cov (row-major, upper
+  // triangle read), uncorrelated with the rest; walk_sigma (empty: a constant): random-walk density per component
+  // in unit / sqrt(s).  Needs max_aux_dim in the options.  Returns the handle.
+  int add_state(const std::vector<double> &val, const std::vector<double> &prior_cov,
+                const std::vector<double> &walk_sigma = {}) {
+    const size_t d = val.size();
+    if (prior_cov.size() != d * d || (!walk_sigma.empty() && walk_sigma.size() != d))
+      throw Error(UVIO_HP_E_ARG, "add_state: size mismatch");
+    int handle = 0;
+    check(uvio_hp_aux_add(h_, (int)d, val.data(), prior_cov.data(), (int)d, walk_sigma.empty() ? nullptr : walk_sigma.data(),
+                          &handle));
+    return handle;
+  }
+  // StateHelper::initialize_invertible for a caller's variable: val0.size() rows res = H_x dx + H_aux dx_aux + noise(R),
+  // H_x row-major over the blocks (as measurement_update's), H_aux square and invertible; the value becomes
+  // val0 + H_aux^-1 res.  Returns the handle.
+  int add_state_from_measurement(const std::vector<double> &val0, const std::vector<std::pair<int, int>> &blocks,
+                                 const std::vector<double> &H_x, const std::vector<double> &H_aux,
+                                 const std::vector<double> &res, const std::vector<double> &R,
+                                 const std::vector<double> &walk_sigma = {}) {
+    std::vector<int> ids, sizes;
+    size_t n = 0;
+    for (const auto &b : blocks) {
+      ids.push_back(b.first);
+      sizes.push_back(b.second);
+      if (b.second > 0) n += (size_t)b.second;
+    }
+    const size_t d = val0.size();
+    if (H_x.size() != d * n || H_aux.size() != d * d || res.size() != d || R.size() != d * d ||
+        (!walk_sigma.empty() && walk_sigma.size() != d))
+      throw Error(UVIO_HP_E_ARG, "add_state_from_measurement: size mismatch");
+    int handle = 0;
+    check(uvio_hp_aux_add_from_measurement(h_, (int)d, val0.data(), (int)blocks.size(), ids.data(), sizes.data(),
+                                           H_x.data(), (int)n, H_aux.data(), (int)d, res.data(), R.data(), (int)d,
+                                           walk_sigma.empty() ? nullptr : walk_sigma.data(), &handle));
+    return handle;
+  }
+  struct AuxState {
+    int id = 0;  // the covariance offset NOW: it moves when clones / landmarks in front are marginalized
+    std::vector<double> value;
+  };
+  AuxState aux_state(int handle) const {
+    AuxState a;
+    int dim = 0;
+    double v[UVIO_HP_AUX_MAX_DIM];
+    check(uvio_hp_aux_get(h_, handle, &a.id, &dim, v));
+    a.value.assign(v, v + dim);
+    return a;
+  }
+  // marginalizes the variable; the handle is dead afterwards
+  void remove_state(int handle) { check(uvio_hp_aux_remove(h_, handle)); }
+  // position_fix with the lever arm p_AinI the aux variable `handle` (3 scalars, add_state): H over
+  // [IMU pose | p_AinI] (position_fix_lever_arm_jacobian), the aux offset read at the call
+  MeasurementResult position_fix_lever_arm(const std::array<double, 3> &p_meas, int handle, const std::array<double, 9> &R,
+                                           double chi2_mult = 1.0) {
+    const std::array<double, 16> x = imu_value();
+    const AuxState a = aux_state(handle);
+    if (a.value.size() != 3) throw Error(UVIO_HP_E_ARG, "position_fix_lever_arm: the variable is not a 3-vector");
+    double h[3], H[27];
+    position_fix_lever_arm_jacobian(x.data(), {a.value[0], a.value[1], a.value[2]}, h, H);
+    int imu_id = 0;
+    for (const auto &m : state_meta())
+      if (m[0] == 0) imu_id = m[1];
+    return measurement_update({{imu_id, 6}, {a.id, 3}}, std::vector<double>(H, H + 27),
                               {p_meas[0] - h[0], p_meas[1] - h[1], p_meas[2] - h[2]},
                               std::vector<double>(R.begin(), R.end()), chi2_mult * chi2_95(3));
   }

@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("UVIO_HP_LIB", os.path.join(ROOT, "uvio_amd", "libuvio
 
 MAX_CAMS = 4
 MAX_ANCHORS = 16
+AUX_MAX_DIM = 8
 
 OK = 0
 E_ARG, E_STATE, E_DEVICE, E_NUMERIC, E_CONFIG, E_ORDER, E_CAPACITY, E_INTERNAL = -1, -2, -3, -4, -5, -6, -7, -8
@@ -60,7 +61,7 @@ class Options(C.Structure):
         ("zupt_only_at_beginning", C.c_int), ("use_klt", C.c_int), ("use_aruco", C.c_int),
         ("record_timing_information", C.c_int), ("record_timing_filepath", C.c_char * 256),
         ("init_window_time", C.c_double), ("init_imu_thresh", C.c_double), ("init_max_disparity", C.c_double),
-        ("init_dyn_use", C.c_int),
+        ("init_dyn_use", C.c_int), ("max_aux_dim", C.c_int),
     ]
 
 
@@ -179,6 +180,15 @@ SIGNATURES = [
                                 _P(_D)]),
     ("ekf_update_r", _I, [_P(_D), _I, _P(_I), _I, _P(_D), _I, _P(_D), _P(_D), _I, _D, _P(_D), _P(_D), _P(_I)]),
     ("chi2_95", _I, [_I, _P(_D)]),
+    ("aux_add", _I, [C.c_void_p, _I, _P(_D), _P(_D), _I, _P(_D), _P(_I)]),
+    ("aux_add_from_measurement", _I, [C.c_void_p, _I, _P(_D), _I, _P(_I), _P(_I), _P(_D), _I, _P(_D), _I, _P(_D),
+                                      _P(_D), _I, _P(_D), _P(_I)]),
+    ("aux_get", _I, [C.c_void_p, _I, _P(_I), _P(_I), _P(_D)]),
+    ("aux_remove", _I, [C.c_void_p, _I]),
+    ("aux_count", _I, [C.c_void_p, _P(_I), _P(_I)]),
+    ("aux_append_p", _I, [_P(_D), _I, _I, _I, _P(_D), _I]),
+    ("aux_init_p", _I, [_P(_D), _I, _I, _I, _P(_I), _I, _P(_D), _I, _P(_D), _P(_D), _P(_D), _I]),
+    ("aux_walk_p", _I, [_P(_D), _I, _I, _I, _P(_I), _P(_I), _P(_D), _D]),
 ]
 
 # uvio_hp_allreduce_fn: int (*)(double *buf, size_t count, void *user)

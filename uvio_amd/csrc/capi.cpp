@@ -386,6 +386,64 @@ int uvio_hp_measurement_update(uvio_hp_t *h, int nvar, const int *ids, const int
   HP_FEED(h, h->e->api_measurement_update(nvar, ids, sizes, H, ldh, r, res, R, ldr, chi2_thr, chi2, applied, dx))
 }
 
+// ---- caller-defined state variables (engine_api.cpp) ----
+int uvio_hp_aux_add(uvio_hp_t *h, int dim, const double *val, const double *prior_cov, int ld, const double *walk_sigma,
+                    int *handle) {
+  if (!h) return UVIO_HP_E_ARG;
+  HP_FEED(h, h->e->api_aux_add(dim, val, prior_cov, ld, walk_sigma, handle))
+}
+int uvio_hp_aux_add_from_measurement(uvio_hp_t *h, int dim, const double *val0, int nvar, const int *ids,
+                                     const int *sizes, const double *H_x, int ldhx, const double *H_aux, int ldha,
+                                     const double *res, const double *R, int ldr, const double *walk_sigma,
+                                     int *handle) {
+  if (!h) return UVIO_HP_E_ARG;
+  HP_FEED(h, h->e->api_aux_add_from_measurement(dim, val0, nvar, ids, sizes, H_x, ldhx, H_aux, ldha, res, R, ldr,
+                                                walk_sigma, handle))
+}
+int uvio_hp_aux_get(uvio_hp_t *h, int handle, int *id, int *dim, double *val) {
+  if (!h) return UVIO_HP_E_ARG;
+  HP_GUARD(h, return h->e->api_aux_get(handle, id, dim, val);)
+}
+int uvio_hp_aux_remove(uvio_hp_t *h, int handle) {
+  if (!h) return UVIO_HP_E_ARG;
+  HP_FEED(h, h->e->api_aux_remove(handle))
+}
+int uvio_hp_aux_count(uvio_hp_t *h, int *n, int *dims_used) {
+  if (!h) return UVIO_HP_E_ARG;
+  return h->e->api_aux_count(n, dims_used);
+}
+
+int uvio_hp_aux_append_p(double *P, int N, int ld, int dim, const double *prior, int ldp) {
+  try {
+    return Engine::aux_append_standalone(P, N, ld, dim, prior, ldp);
+  } catch (const HpError &ex) {
+    return ex.code;
+  } catch (...) {
+    return UVIO_HP_E_DEVICE;
+  }
+}
+int uvio_hp_aux_init_p(double *P, int N, int ld, int dim, const int *H_index, int n, const double *H_x, int ldhx,
+                       const double *H_auxinv, const double *res_unused_or_null, const double *R, int ldr) {
+  (void)res_unused_or_null;  // the residual moves the value only (H_aux^-1 res): the covariance does not read it
+  try {
+    return Engine::aux_init_standalone(P, N, ld, dim, H_index, n, H_x, ldhx, H_auxinv, R, ldr);
+  } catch (const HpError &ex) {
+    return ex.code;
+  } catch (...) {
+    return UVIO_HP_E_DEVICE;
+  }
+}
+int uvio_hp_aux_walk_p(double *P, int N, int ld, int ntab, const int *ids, const int *dims, const double *sigma2,
+                       double dt) {
+  try {
+    return Engine::aux_walk_standalone(P, N, ld, ntab, ids, dims, sigma2, dt);
+  } catch (const HpError &ex) {
+    return ex.code;
+  } catch (...) {
+    return UVIO_HP_E_DEVICE;
+  }
+}
+
 int uvio_hp_debug_last_msckf(uvio_hp_t *h, uint64_t *ids, double *pG, int *status, double *chi2, int cap, int *n) {
   if (!h || !n) return UVIO_HP_E_ARG;
   const auto &v = h->e->last_msckf_;

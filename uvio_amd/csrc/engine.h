@@ -29,7 +29,8 @@
 
 namespace uvhp {
 
-enum VKind { V_IMU = 0, V_VEC = 1, V_QUAT = 2, V_POSE = 3, V_LANDMARK = 4, V_ANCHOR = 5 };
+// V_AUX: a caller-defined additive vector (uvio_hp_aux_add), updated like V_VEC
+enum VKind { V_IMU = 0, V_VEC = 1, V_QUAT = 2, V_POSE = 3, V_LANDMARK = 4, V_ANCHOR = 5, V_AUX = 6 };
 
 // ov_type::Type bookkeeping + value / first estimate
 struct Var {
@@ -461,6 +462,11 @@ double ekf_flops(double N, double n, double r);
 double ekf_bytes(double N, double n, double r);
 // a caller's H (r x n, ld ldh), res (r) and the upper triangle of R (r x r, ld ldr) hold finite numbers only
 bool ekf_R_inputs_finite(const double *H, int ldh, int r, int n, const double *res, const double *R, int ldr);
+// the upper triangle of a caller's d x d matrix (ld) is finite (and, with pos_diag, its diagonal positive)
+bool aux_upper_ok(const double *A, int ld, int d, bool pos_diag);
+// inv (d x d packed) <- A^-1 (d x d, ld lda) by Gauss-Jordan with partial pivoting; false when an entry is not
+// finite or a pivot is not above d * 2^-52 * max |A| (singular)
+bool aux_inverse(const double *A, int lda, int d, double *inv);
 
 class Engine {
  public:
@@ -513,6 +519,12 @@ class Engine {
   static int grid_order_standalone(const uint8_t *resp, const int *off, int ncell, int kmax, int depth,
                                    int *arrangement, int *top);
   static int clahe_standalone(const uint8_t *img, int w, int h, int stride, uint8_t *out);
+  // the aux-state kernels on a caller's host covariance (uvio_hp_aux_append_p / _init_p / _walk_p)
+  static int aux_append_standalone(double *P, int N, int ld, int dim, const double *prior, int ldp);
+  static int aux_init_standalone(double *P, int N, int ld, int dim, const int *H_index, int n, const double *H_x,
+                                 int ldhx, const double *H_auxinv, const double *R, int ldr);
+  static int aux_walk_standalone(double *P, int N, int ld, int ntab, const int *ids, const int *dims,
+                                 const double *sigma2, double dt);
 
  private:
   uvio_hp_options_t o_;
@@ -653,6 +665,15 @@ class Engine {
   int api_measurement_update(int nvar, const int *ids, const int *sizes, const double *H, int ldh, int r,
                              const double *res, const double *R, int ldr, double chi2_thr, double *chi2, int *applied,
                              double *dx);
+  // caller-defined state variables (include/uvio_hp.h uvio_hp_aux_*): appended at N_ on the device
+  // (launch_aux_append / launch_aux_init), removed by marginalize
+  int api_aux_add(int dim, const double *val, const double *prior, int ld, const double *walk_sigma, int *handle);
+  int api_aux_add_from_measurement(int dim, const double *val0, int nvar, const int *ids, const int *sizes,
+                                   const double *H_x, int ldhx, const double *H_aux, int ldha, const double *res,
+                                   const double *R, int ldr, const double *walk_sigma, int *handle);
+  int api_aux_get(int handle, int *id, int *dim, double *val);
+  int api_aux_remove(int handle);
+  int api_aux_count(int *n, int *dims_used) const;
   // the reference routine the host was in when the last call failed (error messages)
   const char *stage() const { return stage_; }
 
@@ -717,6 +738,21 @@ class Engine {
   VarP add_clone_var();
   bool cov_propagate_clone(int s0, int p, const std::vector<int> &iold, const std::vector<double> &Phi,
                            const std::vector<double> &Q, bool do_dt, const double *ddnc);
+  // The aux registry: handle -> variable and its random-walk variances per second (walk_sigma^2).  aux_walkers_
+  // counts the variables with a non-zero density: aux_walk launches nothing while it is 0.
+  struct AuxState {
+    VarP v;
+    double s2[UVIO_HP_AUX_MAX_DIM];
+    bool walks;
+  };
+  std::map<int, AuxState> aux_;
+  int aux_next_ = 1, aux_dims_ = 0, aux_walkers_ = 0;
+  // the checks every aux_add shares (before any device work); returns walk_sigma^2 in s2
+  void aux_check_new(const char *who, int dim, const double *walk_sigma, double *s2) const;
+  int aux_register(int dim, const double *val, const double *s2);
+  // P[i][i] += walk_sigma^2 * dt over every walking aux component, one launch (k_aux_walk); called wherever
+  // timestamp_ advances by dt
+  void aux_walk(double dt);
   void marginalize(const VarP &v);
   // a sequence of marginalize calls as one launch (the same covariance, k_marginalize_multi)
   void marginalize_many(const std::vector<VarP> &ms);

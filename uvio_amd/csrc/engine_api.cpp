@@ -223,4 +223,159 @@ int Engine::api_measurement_update(int nvar, const int *ids, const int *sizes, c
   return 0;
 }
 
+// ---- caller-defined state variables (include/uvio_hp.h uvio_hp_aux_*) ----
+// What uvio does for p_IinU and its anchors at start-up through the host (set_initial_covariance,
+// initialize_invertible_host: two copies of P) for a caller's variable on a running filter: the new rows and columns
+// are written on the device from one staged table, nothing comes back.  Every refusal precedes the device work.
+void Engine::aux_check_new(const char *who, int dim, const double *walk_sigma, double *s2) const {
+  if (!is_initialized_) throw HpError(UVIO_HP_E_STATE, std::string(who) + " before initialization");
+  if (dim < 1 || dim > UVIO_HP_AUX_MAX_DIM) throw HpError(UVIO_HP_E_ARG, std::string(who) + ": dim outside 1 .. 8");
+  for (int k = 0; k < dim; k++) {
+    const double w = walk_sigma ? walk_sigma[k] : 0.0;
+    if (!std::isfinite(w) || w < 0.0)
+      throw HpError(UVIO_HP_E_ARG, std::string(who) + ": walk_sigma must be finite and not negative");
+    s2[k] = w * w;
+  }
+  if (aux_dims_ + dim > o_.max_aux_dim || N_ + dim > d_.ldp)
+    throw HpError(UVIO_HP_E_CAPACITY, std::string(who) + ": the aux dimensions in use (" + std::to_string(aux_dims_) +
+                                          ") plus " + std::to_string(dim) + " exceed max_aux_dim = " +
+                                          std::to_string(o_.max_aux_dim));
+}
+
+// the variable enters vars_ at offset N_ (its covariance rows / columns are already enqueued)
+int Engine::aux_register(int dim, const double *val, const double *s2) {
+  ++p_epoch_;
+  VarP v = std::make_shared<Var>(V_AUX, dim, dim);
+  for (int k = 0; k < dim; k++) v->val[k] = v->fej[k] = val[k];
+  v->id = N_;
+  N_ += dim;
+  vars_.push_back(v);
+  AuxState a{v, {0}, false};
+  for (int k = 0; k < dim; k++) a.s2[k] = s2[k], a.walks = a.walks || s2[k] > 0.0;
+  const int handle = aux_next_++;
+  aux_[handle] = a;
+  aux_dims_ += dim;
+  aux_walkers_ += a.walks ? 1 : 0;
+  odom_invalidate();
+  odom_flush();
+  return handle;
+}
+
+int Engine::api_aux_add(int dim, const double *val, const double *prior, int ld, const double *walk_sigma, int *handle) {
+  stage_ = "aux_add";
+  if (!is_initialized_) throw HpError(UVIO_HP_E_STATE, "aux_add before initialization");
+  if (!val || !prior || !handle) return UVIO_HP_E_ARG;
+  double s2[UVIO_HP_AUX_MAX_DIM];
+  aux_check_new("aux_add", dim, walk_sigma, s2);
+  if (ld < dim) throw HpError(UVIO_HP_E_ARG, "aux_add: leading dimension below the row length");
+  for (int k = 0; k < dim; k++)
+    if (!std::isfinite(val[k])) throw HpError(UVIO_HP_E_ARG, "aux_add: val is not finite");
+  if (!aux_upper_ok(prior, ld, dim, true))
+    throw HpError(UVIO_HP_E_ARG, "aux_add: the upper triangle of prior_cov must be finite with a positive diagonal");
+  void *hv = nullptr;
+  const double *dpr = (const double *)stage_reserve(sizeof(double) * dim * dim, &hv);
+  double *hp = (double *)hv;
+  for (int i = 0; i < dim; i++)
+    for (int j = 0; j < dim; j++) hp[i * dim + j] = j >= i ? prior[(size_t)i * ld + j] : 0.0;
+  stage_flush();
+  launch_aux_append(d_.stream, d_.P, d_.ldp, N_, dim, dpr);
+  *handle = aux_register(dim, val, s2);
+  return 0;
+}
+
+int Engine::api_aux_add_from_measurement(int dim, const double *val0, int nvar, const int *ids, const int *sizes,
+                                         const double *H_x, int ldhx, const double *H_aux, int ldha, const double *res,
+                                         const double *R, int ldr, const double *walk_sigma, int *handle) {
+  stage_ = "StateHelper::initialize_invertible (aux_add_from_measurement)";
+  const char *who = "aux_add_from_measurement";
+  if (!is_initialized_) throw HpError(UVIO_HP_E_STATE, "aux_add_from_measurement before initialization");
+  if (!val0 || !H_aux || !res || !R || !handle || nvar < 0 || (nvar > 0 && (!ids || !sizes))) return UVIO_HP_E_ARG;
+  double s2[UVIO_HP_AUX_MAX_DIM];
+  aux_check_new(who, dim, walk_sigma, s2);
+  long long nl = 0;
+  for (int k = 0; k < nvar; k++) {
+    if (sizes[k] < 1 || ids[k] < 0 || (long long)ids[k] + sizes[k] > N_)
+      throw HpError(UVIO_HP_E_ARG, std::string(who) + ": a block lies outside the state");
+    nl += sizes[k];
+  }
+  if (nl > kAuxMaxCols) throw HpError(UVIO_HP_E_CAPACITY, std::string(who) + ": more than 1215 columns");
+  const int n = (int)nl;
+  if (n > 0 && !H_x) return UVIO_HP_E_ARG;
+  if (ldhx < n || ldha < dim || ldr < dim)
+    throw HpError(UVIO_HP_E_ARG, std::string(who) + ": leading dimension below the row length");
+  bool finite = aux_upper_ok(R, ldr, dim, false);
+  for (int i = 0; i < dim && finite; i++) {
+    finite = std::isfinite(val0[i]) && std::isfinite(res[i]);
+    for (int k = 0; k < n && finite; k++) finite = std::isfinite(H_x[(size_t)i * ldhx + k]);
+  }
+  if (!finite) throw HpError(UVIO_HP_E_ARG, std::string(who) + ": val0, H_x, res or the upper triangle of R is not finite");
+  double Hinv[UVIO_HP_AUX_MAX_DIM * UVIO_HP_AUX_MAX_DIM];
+  if (!aux_inverse(H_aux, ldha, dim, Hinv))
+    throw HpError(UVIO_HP_E_ARG, std::string(who) + ": H_aux is singular or not finite");
+  const size_t nH = (size_t)dim * n, nD = (size_t)dim * dim;
+  const size_t bytes = sizeof(double) * (nH + 2 * nD) + sizeof(int) * (size_t)n;
+  if ((bytes + 255) / 256 * 256 > d_.stg_cap)
+    throw HpError(UVIO_HP_E_CAPACITY, std::string(who) + ": H_x does not fit the upload staging ring");
+  // one staged table: [H_x (dim x n) | H_aux^-1 | R's upper triangle | column map]
+  void *hv = nullptr;
+  const double *dH = (const double *)stage_reserve(bytes, &hv);
+  double *hH = (double *)hv, *hD = hH + nH, *hR = hD + nD;
+  int *hI = (int *)(hR + nD);
+  for (int i = 0; i < dim; i++) {
+    if (n > 0) std::memcpy(hH + (size_t)i * n, H_x + (size_t)i * ldhx, sizeof(double) * n);
+    for (int j = 0; j < dim; j++) {
+      hD[i * dim + j] = Hinv[i * dim + j];
+      hR[i * dim + j] = j >= i ? R[(size_t)i * ldr + j] : 0.0;
+    }
+  }
+  for (int k = 0, c = 0; k < nvar; k++)
+    for (int i = 0; i < sizes[k]; i++) hI[c++] = ids[k] + i;
+  stage_flush();
+  // d_.T (ldp x 64, the propagation's scratch) holds Ma (N x dim)
+  launch_aux_init(d_.stream, d_.P, d_.ldp, N_, dim, dH, n, n, (const int *)(dH + nH + 2 * nD), dH + nH, dH + nH + nD,
+                  d_.T);
+  // new_variable->update(H_Linv * res) (StateHelper.cpp:567)
+  double val[UVIO_HP_AUX_MAX_DIM];
+  for (int a = 0; a < dim; a++) {
+    double dx = 0.0;
+    for (int b = 0; b < dim; b++) dx += Hinv[a * dim + b] * res[b];
+    val[a] = val0[a] + dx;
+  }
+  *handle = aux_register(dim, val, s2);
+  return 0;
+}
+
+int Engine::api_aux_get(int handle, int *id, int *dim, double *val) {
+  if (!is_initialized_) throw HpError(UVIO_HP_E_STATE, "aux_get before initialization");
+  if (!id || !dim) return UVIO_HP_E_ARG;
+  auto it = aux_.find(handle);
+  if (it == aux_.end()) throw HpError(UVIO_HP_E_ARG, "aux_get: no live aux variable has this handle");
+  const Var &v = *it->second.v;
+  *id = v.id;
+  *dim = v.size;
+  if (val) std::memcpy(val, v.val, sizeof(double) * v.size);
+  return 0;
+}
+
+int Engine::api_aux_remove(int handle) {
+  stage_ = "StateHelper::marginalize (aux_remove)";
+  if (!is_initialized_) throw HpError(UVIO_HP_E_STATE, "aux_remove before initialization");
+  auto it = aux_.find(handle);
+  if (it == aux_.end()) throw HpError(UVIO_HP_E_ARG, "aux_remove: no live aux variable has this handle");
+  const AuxState a = it->second;
+  aux_.erase(it);
+  aux_dims_ -= a.v->size;
+  aux_walkers_ -= a.walks ? 1 : 0;
+  marginalize(a.v);
+  odom_invalidate();
+  odom_flush();
+  return 0;
+}
+
+int Engine::api_aux_count(int *n, int *dims_used) const {
+  if (n) *n = (int)aux_.size();
+  if (dims_used) *dims_used = aux_dims_;
+  return 0;
+}
+
 }  // namespace uvhp

@@ -607,13 +607,16 @@ int Engine::propagate_and_clone(double timestamp) {
   const bool do_dt = o_.do_calib_camera_timeoffset != 0;
   const double *ddnc = do_dt ? stage(dnc, 6) : nullptr;
   // propagation and clone in one launch unless the clone is refused below (a clone at this time exists)
+  const double dt_state = timestamp - timestamp_;  // the aux variables' random walk (no launch without one)
   if (clones_.find(timestamp) == clones_.end() && cov_propagate_clone(imu_->id, n, ids, Phi, Qd, do_dt, ddnc)) {
+    aux_walk(dt_state);
     timestamp_ = timestamp;
     last_prop_time_offset_ = t_off_new;
     clones_[timestamp_] = add_clone_var();
     return 0;
   }
   cov_propagate(imu_->id, n, ids, Phi, Qd);
+  aux_walk(dt_state);
   timestamp_ = timestamp;
   last_prop_time_offset_ = t_off_new;
   if (clones_.find(timestamp_) != clones_.end()) return UVIO_HP_E_STATE;
@@ -633,6 +636,7 @@ int Engine::propagate_uwb(double timestamp) {
   std::vector<double> Phi, Qd;
   accumulate_phi(prop, Phi, Qd, n);
   cov_propagate(imu_->id, n, ids, Phi, Qd);
+  aux_walk(timestamp - timestamp_);
   timestamp_ = timestamp;
   return 0;
 }
@@ -871,6 +875,7 @@ int Engine::zupt_try_update(double timestamp) {
   std::vector<double> Phi(36, 0.0), Q(Qb, Qb + 36);
   for (int k = 0; k < 6; k++) Phi[7 * k] = 1.0;
   cov_propagate(imu_->id + 9, 6, bias_ids, Phi, Q);
+  aux_walk(timestamp - timestamp_);  // the aux variables walk over the same window, before the update
   std::vector<double> Hr((size_t)m * (n + 1));
   for (int i = 0; i < m; i++) {
     for (int j = 0; j < n; j++) Hr[(size_t)i * (n + 1) + j] = H[(size_t)i * n + j];

@@ -200,7 +200,9 @@ void Engine::alloc_device() {
   d_.ekf.kp = &kprof_;
   int C = o_.max_clone_size + 2;
   int K = o_.num_cameras;
-  int cap = N_ + 6 * C + 3 * std::max(o_.max_slam_features, 0) + 5 * UVIO_HP_MAX_ANCHORS + 3 + 8;
+  // (max_aux_dim: room for the caller's own variables, uvio_hp_aux_add; 0 leaves every size as it was)
+  int cap = N_ + 6 * C + 3 * std::max(o_.max_slam_features, 0) + 5 * UVIO_HP_MAX_ANCHORS + 3 + 8 +
+            std::max(o_.max_aux_dim, 0);
   cap = (cap + 7) / 8 * 8;
   d_.ldp = cap;
   d_.P = DevBuf<double>((size_t)cap * cap);
@@ -952,6 +954,157 @@ int Engine::clahe_standalone(const uint8_t *img, int w, int h, int stride, uint8
   HP_HIP(hipMemcpyAsync(out, d_img, n, hipMemcpyDeviceToHost, s));
   HP_HIP(hipStreamSynchronize(s));  // nothing in flight when the buffers go (on a throw: freeing device memory waits by itself)
   return 0;
+}
+
+// ---- caller-defined state variables: host helpers, the random walk, the standalone twins ----
+bool aux_upper_ok(const double *A, int ld, int d, bool pos_diag) {
+  for (int i = 0; i < d; i++) {
+    for (int j = i; j < d; j++)
+      if (!std::isfinite(A[(size_t)i * ld + j])) return false;
+    if (pos_diag && !(A[(size_t)i * ld + i] > 0.0)) return false;
+  }
+  return true;
+}
+
+bool aux_inverse(const double *A0, int lda, int d, double *inv) {
+  double A[UVIO_HP_AUX_MAX_DIM * UVIO_HP_AUX_MAX_DIM], amax = 0.0;
+  for (int i = 0; i < d; i++)
+    for (int j = 0; j < d; j++) {
+      const double v = A0[(size_t)i * lda + j];
+      if (!std::isfinite(v)) return false;
+      A[i * d + j] = v;
+      amax = std::max(amax, std::fabs(v));
+      inv[i * d + j] = i == j ? 1.0 : 0.0;
+    }
+  const double tiny = d * 2.220446049250313e-16 * amax;
+  for (int c = 0; c < d; c++) {
+    int piv = c;
+    for (int i = c + 1; i < d; i++)
+      if (std::fabs(A[i * d + c]) > std::fabs(A[piv * d + c])) piv = i;
+    if (!(std::fabs(A[piv * d + c]) > tiny)) return false;
+    for (int j = 0; j < d; j++) std::swap(A[c * d + j], A[piv * d + j]), std::swap(inv[c * d + j], inv[piv * d + j]);
+    const double p = A[c * d + c];
+    for (int j = 0; j < d; j++) A[c * d + j] /= p, inv[c * d + j] /= p;
+    for (int i = 0; i < d; i++)
+      if (i != c) {
+        const double f = A[i * d + c];
+        for (int j = 0; j < d; j++) A[i * d + j] -= f * A[c * d + j], inv[i * d + j] -= f * inv[c * d + j];
+      }
+  }
+  for (int k = 0; k < d * d; k++)
+    if (!std::isfinite(inv[k])) return false;
+  return true;
+}
+
+void Engine::aux_walk(double dt) {
+  if (aux_walkers_ == 0) return;
+  int m = 0;
+  for (const auto &a : aux_)
+    if (a.second.walks) m += a.second.v->size;
+  void *hv = nullptr;
+  char *dv = (char *)stage_reserve(sizeof(double) * m + sizeof(int) * m, &hv);
+  double *hs = (double *)hv;
+  int *hi = (int *)(hs + m);
+  int j = 0;
+  for (const auto &a : aux_)
+    if (a.second.walks)
+      for (int k = 0; k < a.second.v->size; k++, j++) hs[j] = a.second.s2[k], hi[j] = a.second.v->id + k;
+  stage_flush();
+  launch_aux_walk(d_.stream, d_.P, d_.ldp, (const int *)(dv + sizeof(double) * m), (const double *)dv, m, dt);
+  ++p_epoch_;
+}
+
+// the shared front of the twins: the covariance rows with their padding go up, one kernel group runs at the caller's
+// leading dimension, the rows come back
+template <class Fn>
+static int aux_standalone_run(double *P, size_t rows, int ld, Fn &&run) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return UVIO_HP_E_DEVICE;
+  Stream s = Stream::create();
+  DevBuf<double> dP(rows * (size_t)ld);
+  HP_HIP(hipMemcpyAsync(dP, P, sizeof(double) * rows * ld, hipMemcpyHostToDevice, s));
+  run((hipStream_t)s, (double *)dP);
+  HP_HIP(hipGetLastError());
+  HP_HIP(hipMemcpyAsync(P, dP, sizeof(double) * rows * ld, hipMemcpyDeviceToHost, s));
+  HP_HIP(hipStreamSynchronize(s));  // nothing in flight when the buffers go
+  return 0;
+}
+
+int Engine::aux_append_standalone(double *P, int N, int ld, int dim, const double *prior, int ldp) {
+  if (!P || !prior || N < 0 || dim < 1 || dim > UVIO_HP_AUX_MAX_DIM || ldp < dim) return UVIO_HP_E_ARG;
+  if ((long long)N + dim > ld) return UVIO_HP_E_ARG;
+  if (!aux_upper_ok(prior, ldp, dim, true)) return UVIO_HP_E_ARG;
+  std::vector<double> pr((size_t)dim * dim, 0.0);
+  for (int i = 0; i < dim; i++)
+    for (int j = i; j < dim; j++) pr[(size_t)i * dim + j] = prior[(size_t)i * ldp + j];
+  DevBuf<double> dpr;
+  return aux_standalone_run(P, (size_t)N + dim, ld, [&](hipStream_t s, double *dP) {
+    dpr = DevBuf<double>(pr.size());
+    HP_HIP(hipMemcpyAsync(dpr, pr.data(), sizeof(double) * pr.size(), hipMemcpyHostToDevice, s));
+    launch_aux_append(s, dP, ld, N, dim, dpr);
+  });
+}
+
+int Engine::aux_init_standalone(double *P, int N, int ld, int dim, const int *H_index, int n, const double *H_x,
+                                int ldhx, const double *H_auxinv, const double *R, int ldr) {
+  if (!P || !H_auxinv || !R || N < 0 || n < 0 || dim < 1 || dim > UVIO_HP_AUX_MAX_DIM || ldr < dim)
+    return UVIO_HP_E_ARG;
+  if (n > 0 && (!H_index || !H_x || ldhx < n)) return UVIO_HP_E_ARG;
+  if ((long long)N + dim > ld) return UVIO_HP_E_ARG;
+  if (n > kAuxMaxCols) return UVIO_HP_E_CAPACITY;
+  for (int j = 0; j < n; j++)
+    if (H_index[j] < 0 || H_index[j] >= N) return UVIO_HP_E_ARG;
+  if (!aux_upper_ok(R, ldr, dim, false)) return UVIO_HP_E_ARG;
+  // [Hx (dim x n) | Hinv | R upper] as one table
+  const size_t nH = (size_t)dim * n, nD = (size_t)dim * dim;
+  std::vector<double> tab(nH + 2 * nD, 0.0);
+  for (int i = 0; i < dim; i++) {
+    for (int k = 0; k < n; k++)
+      if (!std::isfinite(tab[(size_t)i * n + k] = H_x[(size_t)i * ldhx + k])) return UVIO_HP_E_ARG;
+    for (int j = 0; j < dim; j++) {
+      if (!std::isfinite(tab[nH + (size_t)i * dim + j] = H_auxinv[(size_t)i * dim + j])) return UVIO_HP_E_ARG;
+      if (j >= i) tab[nH + nD + (size_t)i * dim + j] = R[(size_t)i * ldr + j];
+    }
+  }
+  DevBuf<double> dtab, dMa;
+  DevBuf<int> dI;
+  return aux_standalone_run(P, (size_t)N + dim, ld, [&](hipStream_t s, double *dP) {
+    dtab = DevBuf<double>(tab.size());
+    dMa = DevBuf<double>((size_t)std::max(N, 1) * dim);
+    dI = DevBuf<int>((size_t)std::max(n, 1));
+    HP_HIP(hipMemcpyAsync(dtab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, s));
+    if (n > 0) HP_HIP(hipMemcpyAsync(dI, H_index, sizeof(int) * n, hipMemcpyHostToDevice, s));
+    launch_aux_init(s, dP, ld, N, dim, dtab, n, n, dI, dtab + nH, dtab + nH + nD, dMa);
+  });
+}
+
+int Engine::aux_walk_standalone(double *P, int N, int ld, int ntab, const int *ids, const int *dims,
+                                const double *sigma2, double dt) {
+  if (!P || N < 1 || ld < N || ntab < 0 || !std::isfinite(dt) || dt < 0.0) return UVIO_HP_E_ARG;
+  if (ntab > 0 && (!ids || !dims || !sigma2)) return UVIO_HP_E_ARG;
+  std::vector<int> cidx;
+  std::vector<uint8_t> seen((size_t)N, 0);
+  for (int t = 0; t < ntab; t++) {
+    if (dims[t] < 1 || dims[t] > UVIO_HP_AUX_MAX_DIM || ids[t] < 0 || (long long)ids[t] + dims[t] > N)
+      return UVIO_HP_E_ARG;
+    for (int k = 0; k < dims[t]; k++) {
+      if (seen[(size_t)(ids[t] + k)]++) return UVIO_HP_E_ARG;  // (the blocks are disjoint)
+      cidx.push_back(ids[t] + k);
+    }
+  }
+  const int m = (int)cidx.size();
+  for (int j = 0; j < m; j++)
+    if (!std::isfinite(sigma2[j]) || sigma2[j] < 0.0) return UVIO_HP_E_ARG;
+  DevBuf<double> ds2;
+  DevBuf<int> dI;
+  return aux_standalone_run(P, (size_t)N, ld, [&](hipStream_t s, double *dP) {
+    if (m == 0) return;
+    ds2 = DevBuf<double>((size_t)m);
+    dI = DevBuf<int>((size_t)m);
+    HP_HIP(hipMemcpyAsync(ds2, sigma2, sizeof(double) * m, hipMemcpyHostToDevice, s));
+    HP_HIP(hipMemcpyAsync(dI, cidx.data(), sizeof(int) * m, hipMemcpyHostToDevice, s));
+    launch_aux_walk(s, dP, ld, dI, ds2, m, dt);
+  });
 }
 
 }  // namespace uvhp

@@ -154,6 +154,19 @@ void launch_check_diag(hipStream_t s, const double *P, int ld, int N, int *neg);
 // covariance indices idx (device, any order, repeats allowed, each in [0, N) of P)
 void launch_marginal_gather(hipStream_t s, const double *P, int ld, const int *idx, int m, double *out);
 
+// ---- caller-defined ("auxiliary") state variables (include/uvio_hp.h uvio_hp_aux_*; kernels_cov.hip) ----
+constexpr int kAuxMaxDim = 8;      // UVIO_HP_AUX_MAX_DIM
+constexpr int kAuxMaxCols = 1215;  // columns of H_x (uvio_hp_measurement_update's limit)
+// StateHelper::set_initial_covariance (StateHelper.cpp:199-223) of a new variable at N: rows / columns N .. N+d-1 <-
+// zeros against [0, N), prior (d x d packed, device, upper triangle read) mirrored into the block.  N + d <= ld
+void launch_aux_append(hipStream_t s, double *P, int ld, int N, int d, const double *prior);
+// StateHelper::initialize_invertible (StateHelper.cpp:484-577) of a new variable at N: Hx (d x n, ld ldh), hidx (n),
+// Hinv = H_aux^-1 (d x d packed), R (d x d packed, upper triangle read), all device; Ma: N x d scratch.  Two launches
+void launch_aux_init(hipStream_t s, double *P, int ld, int N, int d, const double *Hx, int ldh, int n, const int *hidx,
+                     const double *Hinv, const double *R, double *Ma);
+// random walk of m components: P[cidx[j]][cidx[j]] += s2[j] * dt (rounded product, then rounded sum); cidx distinct
+void launch_aux_walk(hipStream_t s, double *P, int ld, const int *cidx, const double *s2, int m, double dt);
+
 // MSCKF / SLAM per-feature linearization: triangulation (+LM), Jacobian, nullspace, chi2, rows to H_all
 // zero (optional): set to 0 (the accepted-feature count of the batch's gate, which k_chi2_small only adds to)
 void launch_feature_linearize(hipStream_t s, const DBatchParams &bp, const DFeat *feats, const DMeas *meas,

@@ -302,6 +302,145 @@ void launch_marginal_gather(hipStream_t s, const double *P, int ld, const int *i
 }
 
 // ----------------------------------------------------------------------------------------------
+// Caller-defined state variables (include/uvio_hp.h uvio_hp_aux_*): a d-wide variable, d <= kAuxMaxDim, appended at
+// N.  Every product and sum below is rounded by itself (__dmul_rn / __dadd_rn, never contracted into an fma) and
+// the summation orders are fixed, so a float64 replay on the host (tests/aux_ref.py) forms the same numbers.
+//
+// k_aux_append: StateHelper::set_initial_covariance (StateHelper.cpp:199-223) of the new variable alone: one thread
+// per (row i of [0, N + d), new column b); zeros against the old state, the prior's upper triangle mirrored.
+__global__ void k_aux_append(double *__restrict__ P, int ld, int N, int d, const double *__restrict__ prior) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (N + d) * d) return;
+  const int i = idx / d, b = idx % d;
+  if (i < N) {
+    P[(size_t)i * ld + N + b] = 0.0;
+    P[(size_t)(N + b) * ld + i] = 0.0;
+  } else {
+    const int a = i - N;
+    P[(size_t)i * ld + N + b] = (a <= b) ? prior[a * d + b] : prior[b * d + a];
+  }
+}
+void launch_aux_append(hipStream_t s, double *P, int ld, int N, int d, const double *prior) {
+  const int n = (N + d) * d, bs = 256;
+  hipLaunchKernelGGL(k_aux_append, dim3((n + bs - 1) / bs), dim3(bs), 0, s, P, ld, N, d, prior);
+}
+
+// The sum of a wavefront's per-lane partials, the same in every lane: six exchange steps at lane distance 32, 16,
+// 8, 4, 2, 1 -- v <- v + v[lane ^ o], and a + b == b + a, so the two partners of a step hold the same value
+__device__ __forceinline__ double aux_wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = __dadd_rn(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// k_aux_init: StateHelper::initialize_invertible (StateHelper.cpp:484-577) of the new variable, old-state rows.
+// One wavefront per covariance row i < N (kAuxInitRows rows per workgroup), as k_di_M's GEMV:
+//   Ma[i][b] = sum_k P[i][hidx[k]] Hx[b][k]: lane l adds its columns k = l, l + 64, .. in ascending k to a partial
+//              that starts at 0.0, then aux_wave_sum over the 64 partials
+//   P[i][N + a] = P[N + a][i] = 0.0 - (sum_b Ma[i][b] Hinv[a][b]), b ascending from 0.0, by lane a (0.0 - x: a
+//              zero sum is stored as +0.0, as k_aux_append stores it)
+// P is read at columns < N and written at rows / columns >= N only.
+constexpr int kAuxInitRows = 4;
+__global__ void __launch_bounds__(64 * kAuxInitRows) k_aux_init(double *__restrict__ P, int ld, int N, int d,
+                                                              const double *__restrict__ Hx, int ldh, int n,
+                                                              const int *__restrict__ hidx,
+                                                              const double *__restrict__ Hinv, double *__restrict__ Ma) {
+  const int lane = threadIdx.x & 63, i = blockIdx.x * kAuxInitRows + (threadIdx.x >> 6);
+  if (i >= N) return;  // (the whole wavefront)
+  const double *Pi = P + (size_t)i * ld;
+  double acc[kAuxMaxDim];
+#pragma unroll
+  for (int b = 0; b < kAuxMaxDim; b++) acc[b] = 0.0;
+  for (int k = lane; k < n; k += 64) {
+    const double p = Pi[hidx[k]];
+#pragma unroll
+    for (int b = 0; b < kAuxMaxDim; b++)
+      if (b < d) acc[b] = __dadd_rn(acc[b], __dmul_rn(p, Hx[(size_t)b * ldh + k]));
+  }
+#pragma unroll
+  for (int b = 0; b < kAuxMaxDim; b++)
+    if (b < d) acc[b] = aux_wave_sum(acc[b]);
+  if (lane < d) {
+    double mine = acc[0], x = 0.0;
+#pragma unroll
+    for (int b = 0; b < kAuxMaxDim; b++) {
+      if (b == lane) mine = acc[b];
+      if (b < d) x = __dadd_rn(x, __dmul_rn(acc[b], Hinv[lane * d + b]));
+    }
+    Ma[(size_t)i * d + lane] = mine;
+    x = __dsub_rn(0.0, x);
+    P[(size_t)i * ld + N + lane] = x;
+    P[(size_t)(N + lane) * ld + i] = x;
+  }
+}
+
+// k_aux_init_own: the variable's own d x d block, one workgroup of four wavefronts, from Ma (k_aux_init's):
+//   M[a][b] = (sum_k Hx[a][k] Ma[hidx[k]][b]) + R[a][b] for a <= b, one wavefront per pair (the pairs in row-major
+//             order of the upper triangle, pair p by wavefront p % 4), the sum over k as in k_aux_init; R is added
+//             last; M[b][a] = M[a][b] (M.selfadjointView<Upper>())
+//   U[c][b]   = sum_e M[c][e] Hinv[b][e], e ascending from 0.0
+//   own[a][b] = sum_c Hinv[a][c] U[c][b], c ascending from 0.0, for a <= b, stored at both [a][b] and [b][a]
+__global__ void __launch_bounds__(256) k_aux_init_own(double *__restrict__ P, int ld, int N, int d,
+                                                      const double *__restrict__ Hx, int ldh, int n,
+                                                      const int *__restrict__ hidx, const double *__restrict__ Hinv,
+                                                      const double *__restrict__ R, const double *__restrict__ Ma) {
+  __shared__ double Ms[kAuxMaxDim * kAuxMaxDim], Us[kAuxMaxDim * kAuxMaxDim];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, t = threadIdx.x;
+  for (int p = wid; p < d * (d + 1) / 2; p += 4) {
+    int a = 0, rem = p;
+    while (rem >= d - a) rem -= d - a, a++;
+    const int b = a + rem;
+    double acc = 0.0;
+    for (int k = lane; k < n; k += 64)
+      acc = __dadd_rn(acc, __dmul_rn(Hx[(size_t)a * ldh + k], Ma[(size_t)hidx[k] * d + b]));
+    acc = aux_wave_sum(acc);
+    if (lane == 0) {
+      const double v = __dadd_rn(acc, R[a * d + b]);
+      Ms[a * d + b] = v;
+      Ms[b * d + a] = v;
+    }
+  }
+  __syncthreads();
+  if (t < d * d) {
+    const int c = t / d, b = t % d;
+    double s = 0.0;
+    for (int e = 0; e < d; e++) s = __dadd_rn(s, __dmul_rn(Ms[c * d + e], Hinv[b * d + e]));
+    Us[c * d + b] = s;
+  }
+  __syncthreads();
+  if (t < d * d) {
+    const int a = t / d, b = t % d;
+    if (a <= b) {
+      double s = 0.0;
+      for (int c = 0; c < d; c++) s = __dadd_rn(s, __dmul_rn(Hinv[a * d + c], Us[c * d + b]));
+      P[(size_t)(N + a) * ld + N + b] = s;
+      P[(size_t)(N + b) * ld + N + a] = s;
+    }
+  }
+}
+void launch_aux_init(hipStream_t s, double *P, int ld, int N, int d, const double *Hx, int ldh, int n, const int *hidx,
+                     const double *Hinv, const double *R, double *Ma) {
+  if (N > 0)
+    hipLaunchKernelGGL(k_aux_init, dim3((N + kAuxInitRows - 1) / kAuxInitRows), dim3(64 * kAuxInitRows), 0, s, P, ld, N,
+                       d, Hx, ldh, n, hidx, Hinv, Ma);
+  hipLaunchKernelGGL(k_aux_init_own, dim3(1), dim3(256), 0, s, P, ld, N, d, Hx, ldh, n, hidx, Hinv, R, Ma);
+}
+
+// k_aux_walk: the random walk of every walking aux component over dt in one launch, one thread per component:
+// P[i][i] <- P[i][i] + fl(s2 * dt), two roundings (the host's float64 replay is bit-identical)
+__global__ void k_aux_walk(double *__restrict__ P, int ld, const int *__restrict__ cidx, const double *__restrict__ s2,
+                           int m, double dt) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  double *pd = P + (size_t)cidx[j] * ld + cidx[j];
+  *pd = __dadd_rn(*pd, __dmul_rn(s2[j], dt));
+}
+void launch_aux_walk(hipStream_t s, double *P, int ld, const int *cidx, const double *s2, int m, double dt) {
+  if (m <= 0) return;
+  hipLaunchKernelGGL(k_aux_walk, dim3((m + 63) / 64), dim3(64), 0, s, P, ld, cidx, s2, m, dt);
+}
+
+// ----------------------------------------------------------------------------------------------
 // Compression: Gram partials.  Grid: (upper tile pairs, row chunks).  Tile 32x32, 256 threads,
 // each thread 2x2 outputs.  A is m x ncol, row-major, ld = ldh.
 constexpr int GT = 32;         // tile edge

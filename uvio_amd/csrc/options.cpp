@@ -333,6 +333,7 @@ void options_default(uvio_hp_options_t *o) {
   o->init_imu_thresh = 1.0;
   o->init_max_disparity = 1.0;
   o->init_dyn_use = 0;
+  o->max_aux_dim = 0;
 }
 
 int options_load(const char *path, uvio_hp_options_t *o, std::string *err) {
@@ -404,6 +405,7 @@ int options_load(const char *path, uvio_hp_options_t *o, std::string *err) {
   est.get({"init_imu_thresh"}, o->init_imu_thresh);
   est.get({"init_max_disparity"}, o->init_max_disparity);
   est.getb({"init_dyn_use"}, o->init_dyn_use);
+  est.get({"max_aux_dim"}, o->max_aux_dim);
   est.get({"grid_x"}, o->grid_x);
   est.get({"grid_y"}, o->grid_y);
   est.get({"min_px_dist"}, o->min_px_dist);

@@ -366,6 +366,75 @@ class VioManager:
         return self.measurement_update([(int(imu[1]), 6)], H, np.asarray(p_meas, dtype=np.float64) - pred, R,
                                        chi2_mult * chi2_95(3))
 
+    # ---- state variables of the caller's own (uvio_hp_aux_*): a lever arm, a bias, a frame offset, a scale ----
+    @staticmethod
+    def _walk(walk_sigma, dim):
+        if walk_sigma is None:
+            return None, None
+        w = np.ascontiguousarray(np.broadcast_to(np.asarray(walk_sigma, dtype=np.float64), (dim,)))
+        return w, _dp(w)
+
+    def add_state(self, val, prior_cov, walk_sigma=None):
+        """A new additive state variable (1 .. 8 scalars) with value val and prior covariance prior_cov (upper
+        triangle read), uncorrelated with the rest; walk_sigma: random-walk density per component in unit / sqrt(s)
+        (None: a constant).  Needs options.max_aux_dim.  Returns the handle."""
+        val = np.ascontiguousarray(val, dtype=np.float64).reshape(-1)
+        d = val.size
+        pr = np.ascontiguousarray(np.asarray(prior_cov, dtype=np.float64).reshape(d, d))
+        w, wp = self._walk(walk_sigma, d)
+        h = C.c_int(0)
+        self._check(self._call("aux_add", self._h, d, _dp(val), _dp(pr), d, wp, C.byref(h)), "aux_add")
+        return h.value
+
+    def add_state_from_measurement(self, val0, blocks, H_x, H_aux, res, R, walk_sigma=None):
+        """StateHelper::initialize_invertible for a caller's variable: dim rows res = H_x dx + H_aux dx_aux + noise(R),
+        H_x over blocks = [(covariance id, size), ...], H_aux (dim, dim) invertible.  The value becomes
+        val0 + H_aux^-1 res, correlated with the state through H_x.  Returns the handle."""
+        val0 = np.ascontiguousarray(val0, dtype=np.float64).reshape(-1)
+        d = val0.size
+        ids = np.ascontiguousarray([b[0] for b in blocks], dtype=np.int32)
+        sizes = np.ascontiguousarray([b[1] for b in blocks], dtype=np.int32)
+        n = int(sizes.sum()) if len(blocks) else 0
+        H_x = np.ascontiguousarray(np.asarray(H_x, dtype=np.float64).reshape(d, n))
+        H_aux = np.ascontiguousarray(np.asarray(H_aux, dtype=np.float64).reshape(d, d))
+        res = np.ascontiguousarray(res, dtype=np.float64).reshape(d)
+        R = np.ascontiguousarray(np.asarray(R, dtype=np.float64).reshape(d, d))
+        w, wp = self._walk(walk_sigma, d)
+        h = C.c_int(0)
+        ip = C.POINTER(C.c_int)
+        self._check(self._call("aux_add_from_measurement", self._h, d, _dp(val0), len(blocks), ids.ctypes.data_as(ip),
+                               sizes.ctypes.data_as(ip), _dp(H_x), max(n, 1), _dp(H_aux), d, _dp(res), _dp(R), d, wp,
+                               C.byref(h)), "aux_add_from_measurement")
+        return h.value
+
+    def aux_state(self, handle):
+        """(covariance offset, value) of an aux variable now.  The offset moves when clones or landmarks in front
+        of the variable are marginalized: ask before building an H."""
+        vid, dim = C.c_int(), C.c_int()
+        val = np.zeros(N.AUX_MAX_DIM)
+        self._check(self._call("aux_get", self._h, int(handle), C.byref(vid), C.byref(dim), _dp(val)), "aux_get")
+        return vid.value, val[:dim.value].copy()
+
+    def remove_state(self, handle):
+        """Marginalize an aux variable; the handle is dead afterwards."""
+        self._check(self._call("aux_remove", self._h, int(handle)), "aux_remove")
+
+    def aux_count(self):
+        """(number of live aux variables, sum of their dimensions)"""
+        n, d = C.c_int(), C.c_int()
+        self._check(self._call("aux_count", self._h, C.byref(n), C.byref(d)), "aux_count")
+        return n.value, d.value
+
+    def position_fix_lever_arm(self, p_meas, handle, R, chi2_mult=1.0):
+        """position_fix with the antenna's lever arm p_AinI an aux variable (add_state): z = p_IinG + R_ItoG p_AinI,
+        H over [IMU pose (6) | p_AinI (3)] (position_fix_lever_arm_jacobian), the aux offset read now."""
+        x = self.get_imu_state()[1]
+        aid, arm = self.aux_state(handle)
+        pred, H = position_fix_lever_arm_jacobian(x[0:4], x[4:7], arm)
+        imu = [m for m in self.get_state_vector()[1] if m[0] == 0][0]
+        return self.measurement_update([(int(imu[1]), 6), (aid, 3)], H, np.asarray(p_meas, dtype=np.float64) - pred, R,
+                                       chi2_mult * chi2_95(3))
+
     # ---- getters ----
     def initialized(self):
         """VioManager::initialized (VioManager.h:99): initialize_with_gt ran or an initializer succeeded."""
@@ -744,6 +813,63 @@ def position_fix_jacobian(q_GtoI, p_IinG, p_SinI):
     s = np.asarray(p_SinI, dtype=np.float64)
     S = np.array([[0.0, -s[2], s[1]], [s[2], 0.0, -s[0]], [-s[1], s[0], 0.0]])
     return np.asarray(p_IinG, dtype=np.float64) + Rm.T @ s, np.hstack([-Rm.T @ S, np.eye(3)])
+
+
+def position_fix_lever_arm_jacobian(q_GtoI, p_IinG, p_AinI):
+    """position_fix_jacobian with the lever arm a state variable: h(x) = p_IinG + R_ItoG p_AinI (R_ItoG = R_GtoI^T) and
+    its (3, 9) Jacobian over [dtheta, dp, dp_AinI]: [-R_ItoG [p_AinI]x, I, R_ItoG].  Returns (h, H)."""
+    h, H = position_fix_jacobian(q_GtoI, p_IinG, p_AinI)
+    return h, np.hstack([H, quat_2_Rot(q_GtoI).T])
+
+
+def _padded(P, rows, ld):
+    """P in the top-left corner of a (rows, ld) array whose other entries are a recognizable padding"""
+    P = np.asarray(P, dtype=np.float64)
+    buf = np.full((rows, ld), -7.25)
+    buf[:P.shape[0], :P.shape[1]] = P
+    return buf
+
+
+def aux_append_p(P, prior, ld=None):
+    """uvio_hp_aux_append_p: k_aux_append on a standalone covariance.  P (N, N), prior (d, d') with d' >= d its
+    leading dimension.  Returns the (N + d, ld) buffer as it came back (padding included)."""
+    prior = np.ascontiguousarray(prior, dtype=np.float64)
+    Nn, d = np.shape(P)[0], prior.shape[0]
+    ld = Nn + d if ld is None else int(ld)
+    buf = _padded(P, Nn + d, ld)
+    N.check(N.load().uvio_hp_aux_append_p(_dp(buf), Nn, ld, d, _dp(prior), prior.shape[1]), what="uvio_hp_aux_append_p")
+    return buf
+
+
+def aux_init_p(P, H_index, H_x, H_auxinv, R, ld=None):
+    """uvio_hp_aux_init_p: k_aux_init on a standalone covariance.  H_x (d, n) over the columns H_index, H_auxinv
+    (d, d), R (d, d') with d' >= d.  Returns the (N + d, ld) buffer as it came back."""
+    H_x = np.ascontiguousarray(H_x, dtype=np.float64)
+    Hi = np.ascontiguousarray(H_auxinv, dtype=np.float64)
+    R = np.ascontiguousarray(R, dtype=np.float64)
+    idx = np.ascontiguousarray(H_index, dtype=np.int32)
+    Nn, (d, n) = np.shape(P)[0], H_x.shape
+    ld = Nn + d if ld is None else int(ld)
+    buf = _padded(P, Nn + d, ld)
+    rc = N.load().uvio_hp_aux_init_p(_dp(buf), Nn, ld, d, idx.ctypes.data_as(C.POINTER(C.c_int)), n, _dp(H_x),
+                                     max(H_x.shape[1], 1), _dp(Hi), None, _dp(R), R.shape[1])
+    N.check(rc, what="uvio_hp_aux_init_p")
+    return buf
+
+
+def aux_walk_p(P, ids, dims, sigma2, dt, ld=None):
+    """uvio_hp_aux_walk_p: k_aux_walk on a standalone covariance.  Returns the (N, ld) buffer as it came back."""
+    ids = np.ascontiguousarray(ids, dtype=np.int32)
+    dims = np.ascontiguousarray(dims, dtype=np.int32)
+    s2 = np.ascontiguousarray(sigma2, dtype=np.float64)
+    Nn = np.shape(P)[0]
+    ld = Nn if ld is None else int(ld)
+    buf = _padded(P, Nn, ld)
+    ip = C.POINTER(C.c_int)
+    rc = N.load().uvio_hp_aux_walk_p(_dp(buf), Nn, ld, len(ids), ids.ctypes.data_as(ip), dims.ctypes.data_as(ip), _dp(s2),
+                                     float(dt))
+    N.check(rc, what="uvio_hp_aux_walk_p")
+    return buf
 
 
 def compress(A):
