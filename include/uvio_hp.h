@@ -448,8 +448,8 @@ int uvio_hp_propagate(uvio_hp_t *h, double t);
  * UVIO_HP_E_NUMERIC (fatal, as everywhere): a negative covariance diagonal after an accepted update.
  * Serialized with the feeds.  When applied the odometry cache is republished, as after uvio_hp_msckf_update.
  * A state variable of the caller's own (a sensor bias, a lever arm) is added with uvio_hp_aux_add below and named
- * here like any other block.  Not covered: buffering such measurements inside uvio_hp_feed_camera as UWB messages
- * are, and chains of relinearized updates on the device. */
+ * here like any other block.  A position fix can instead be buffered inside the frame and relinearized on the device
+ * (uvio_hp_feed_position below); for any other model this call, after uvio_hp_propagate, is the one to use. */
 int uvio_hp_measurement_update(uvio_hp_t *h, int nvar, const int *ids, const int *sizes, const double *H, int ldh, int r,
                                const double *res, const double *R, int ldr, double chi2_thr, double *chi2, int *applied,
                                double *dx);
@@ -493,6 +493,35 @@ int uvio_hp_aux_get(uvio_hp_t *h, int handle, int *id, int *dim, double *val);
 int uvio_hp_aux_remove(uvio_hp_t *h, int handle);
 /* number of live aux variables and the sum of their dimensions (either pointer may be NULL) */
 int uvio_hp_aux_count(uvio_hp_t *h, int *n, int *dims_used);
+
+/* ---- buffered position fixes (GPS / mocap position, an altimeter, a planar positioning system) ----
+ * What the reference does for its UWB messages (UVioManager.cpp:178-188), for the commonest external measurement:
+ * a fix is queued, and the next uvio_hp_feed_camera / _simulation propagates to each queued time in (state time,
+ * frame time) and updates there, merged in ascending time with the buffered UWB messages (at equal times the UWB
+ * message first, then the fixes in feed order).  The model is a position fix of a sensor point S on the body,
+ *     z = C (p_IinG + R_GtoI^T s) + noise(R),
+ * r = 1 .. 3 rows, C r x 3 row-major (I: GPS / mocap; e_z^T: an altimeter; two rows: planar), R r x r (leading
+ * dimension ldr, upper triangle read), s the constant lever arm p_SinI[3] (aux_handle <= 0) or a live 3-dimensional
+ * aux variable (aux_handle > 0; p_SinI is then ignored and may be NULL) whose value and covariance offset are
+ * looked up at replay.  H over the error state is C [-R_GtoI^T [s]x | I | R_GtoI^T] (JPL left error), the last
+ * block only for an aux lever arm.  Each distinct time runs uvio_hp_propagate's propagation (both quirks, the aux
+ * random walk); the fixes of one time then form one device chain with one readback per 8 fixes, each fix linearized at
+ * the state the previous one left.  Gate: chi2_mult * uvio_hp_chi2_95(r) (chi2_mult = INFINITY: no gate).
+ * t is in the clock uvio_hp_propagate takes.  *queued = 0 with a return of 0 when the filter is not initialized or t is
+ * not after the state time (uvio_hp_feed_uwb's behaviour).  UVIO_HP_E_ARG, before anything is stored: null pointers,
+ * r outside 1 .. 3, ldr < r, a non-finite t, C, z, read triangle of R or p_SinI, a diagonal of R that is not positive,
+ * a chi2_mult that is not positive (or NaN), an aux handle that is dead or not 3-dimensional.  UVIO_HP_E_CAPACITY: 256
+ * fixes are already queued (host memory).  A frame that ends in a zero-velocity update leaves the queue alone; fixes
+ * at or before the frame time are erased afterwards.  UVIO_HP_E_NUMERIC (fatal) from the frame: a negative covariance
+ * diagonal after an applied fix.  Serialized with the feeds; with feature sharding every rank makes the call. */
+int uvio_hp_feed_position(uvio_hp_t *h, double t, int r, const double *C, const double *z, const double *R, int ldr,
+                          const double *p_SinI, int aux_handle, double chi2_mult, int *queued);
+/* The fixes consumed by the last camera or simulation feed, in processing order: time, chi2 and status (any array may
+ * be NULL).  Status 0: applied.  1: gated (chi2 above the threshold).  2: dropped (its time was not after the state time
+ * at replay, or equal to the frame time, or the propagation to it failed for lack of IMU readings).  3: refused (S not
+ * positive definite or a NaN chi2, or the aux handle was removed after queueing); the state is untouched.
+ * *n is always written; UVIO_HP_E_CAPACITY when *n > cap (nothing else is written). */
+int uvio_hp_get_position_results(uvio_hp_t *h, double *t, double *chi2, int *status, int cap, int *n);
 
 /* ---- feature-sharded MSCKF update across GPUs (BASELINE.json configs 4-5) ----
  * One process per GPU, each with its own handle fed the same measurement stream (the filter state is
@@ -568,6 +597,16 @@ int uvio_hp_aux_init_p(double *P, int N, int ld, int dim, const int *H_index, in
                        const double *H_auxinv, const double *res_unused_or_null, const double *R, int ldr);
 int uvio_hp_aux_walk_p(double *P, int N, int ld, int ntab, const int *ids, const int *dims, const double *sigma2,
                        double dt);
+/* The three kernels of the buffered position-fix chain (uvio_hp_feed_position) for one fix on a caller's host
+ * covariance at a caller's pose: P holds N rows of ld doubles (ld >= N >= 6), uploaded and returned with their
+ * padding; the IMU pose's 6 error columns start at imu_id, q[4] = q_GtoI (JPL), p[3] = p_IinG, s[3] the lever arm,
+ * whose 3 columns start at aux_id (aux_id < 0: a constant lever arm; the blocks must not overlap).  r, C, z, R, ldr as
+ * for uvio_hp_feed_position; chi2_thr positive (INFINITY: no gate).  dx (N) receives the correction, zeros when not
+ * applied.  UVIO_HP_E_ARG before any device work for bad arguments, and after it when S is not positive definite (P
+ * unchanged); UVIO_HP_E_NUMERIC for a negative diagonal after the update. */
+int uvio_hp_debug_position_update_p(double *P, int N, int ld, int imu_id, const double *q, const double *p, int aux_id,
+                                    const double *s, int r, const double *C, const double *z, const double *R, int ldr,
+                                    double chi2_thr, double *dx, double *chi2, int *applied);
 /* boost::math::quantile(chi_squared(dof), 0.95), the table every reference updater multiplies its chi2_multipler
  * into (UpdaterMSCKF.cpp:52-55, UpdaterSLAM.cpp:55-58, UpdaterZeroVelocity.cpp:59-62, UpdaterUWB.h:33-36), for
  * dof 1 .. 999; UVIO_HP_E_ARG outside that range. */

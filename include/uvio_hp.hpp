@@ -16,6 +16,7 @@
  *   Manager::measurement_update    <- StateHelper::EKFUpdate (StateHelper.h:88) behind UpdaterUWB.cpp:67-79's gate
  *   Manager::add_state             <- StateHelper::set_initial_covariance (StateHelper.cpp:199) for a variable of the caller's
  *   Manager::add_state_from_measurement <- StateHelper::initialize_invertible (StateHelper.cpp:484)
+ *   Manager::feed_position         <- the UWB buffer-and-replay of UVioManager.cpp:178-188 for a position fix
  */
 #ifndef UVIO_HP_HPP
 #define UVIO_HP_HPP
@@ -468,6 +469,37 @@ class Manager {
     return measurement_update({{imu_id, 6}, {a.id, 3}}, std::vector<double>(H, H + 27),
                               {p_meas[0] - h[0], p_meas[1] - h[1], p_meas[2] - h[2]},
                               std::vector<double>(R.begin(), R.end()), chi2_mult * chi2_95(3));
+  }
+
+  // ---- buffered position fixes (uvio_hp_feed_position): replayed in time order inside the next frame ----
+  // z = C (p_IinG + R_GtoI^T s) + noise(R): z.size() = r rows (1 .. 3), C row-major r x 3, R row-major r x r (upper
+  // triangle read), s the constant lever arm p_SinI or, with aux_handle > 0, a 3-scalar variable of add_state; gated at
+  // chi2_mult * chi2_95(r) (INFINITY: no gate).  True when queued; false when the filter is not initialized or t is
+  // not after the state time
+  bool feed_position(double t, const std::vector<double> &z, const std::vector<double> &C, const std::vector<double> &R,
+                     const std::array<double, 3> &p_SinI = {0.0, 0.0, 0.0}, int aux_handle = 0, double chi2_mult = 1.0) {
+    const size_t r = z.size();
+    if (C.size() != 3 * r || R.size() != r * r) throw Error(UVIO_HP_E_ARG, "feed_position: size mismatch");
+    int queued = 0;
+    check(uvio_hp_feed_position(h_, t, (int)r, C.data(), z.data(), R.data(), (int)r, p_SinI.data(), aux_handle, chi2_mult,
+                                &queued));
+    return queued != 0;
+  }
+  struct PositionResult {
+    double t = 0.0, chi2 = 0.0;
+    int status = 0;  // 0 applied, 1 gated, 2 dropped, 3 refused
+  };
+  // the fixes the last camera / simulation feed consumed, in processing order
+  std::vector<PositionResult> position_results() const {
+    int n = 0;
+    const int rc = uvio_hp_get_position_results(h_, nullptr, nullptr, nullptr, 0, &n);
+    if (rc != UVIO_HP_E_CAPACITY) check(rc);
+    std::vector<double> t((size_t)n), c((size_t)n);
+    std::vector<int> s((size_t)n);
+    if (n > 0) check(uvio_hp_get_position_results(h_, t.data(), c.data(), s.data(), n, &n));
+    std::vector<PositionResult> out((size_t)n);
+    for (size_t k = 0; k < out.size(); k++) out[k].t = t[k], out[k].chi2 = c[k], out[k].status = s[k];
+    return out;
   }
 
   uvio_hp_t *handle() { return h_; }

@@ -189,6 +189,10 @@ SIGNATURES = [
     ("aux_append_p", _I, [_P(_D), _I, _I, _I, _P(_D), _I]),
     ("aux_init_p", _I, [_P(_D), _I, _I, _I, _P(_I), _I, _P(_D), _I, _P(_D), _P(_D), _P(_D), _I]),
     ("aux_walk_p", _I, [_P(_D), _I, _I, _I, _P(_I), _P(_I), _P(_D), _D]),
+    ("feed_position", _I, [C.c_void_p, _D, _I, _P(_D), _P(_D), _P(_D), _I, _P(_D), _I, _D, _P(_I)]),
+    ("get_position_results", _I, [C.c_void_p, _P(_D), _P(_D), _P(_I), _I, _P(_I)]),
+    ("debug_position_update_p", _I, [_P(_D), _I, _I, _I, _P(_D), _P(_D), _I, _P(_D), _I, _P(_D), _P(_D), _P(_D), _I, _D,
+                                     _P(_D), _P(_D), _P(_I)]),
 ]
 
 # uvio_hp_allreduce_fn: int (*)(double *buf, size_t count, void *user)

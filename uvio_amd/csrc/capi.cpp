@@ -444,6 +444,37 @@ int uvio_hp_aux_walk_p(double *P, int N, int ld, int ntab, const int *ids, const
   }
 }
 
+// ---- buffered position fixes (engine_update.cpp) ----
+int uvio_hp_feed_position(uvio_hp_t *h, double t, int r, const double *C, const double *z, const double *R, int ldr,
+                          const double *p_SinI, int aux_handle, double chi2_mult, int *queued) {
+  if (!h) return UVIO_HP_E_ARG;
+  HP_FEED(h, h->e->feed_position(t, r, C, z, R, ldr, p_SinI, aux_handle, chi2_mult, queued))
+}
+int uvio_hp_get_position_results(uvio_hp_t *h, double *t, double *chi2, int *status, int cap, int *n) {
+  if (!h || !n) return UVIO_HP_E_ARG;
+  const auto &v = h->e->position_results();
+  *n = (int)v.size();
+  if (*n > cap) return UVIO_HP_E_CAPACITY;
+  for (int k = 0; k < *n; k++) {
+    if (t) t[k] = v[(size_t)k].t;
+    if (chi2) chi2[k] = v[(size_t)k].chi2;
+    if (status) status[k] = v[(size_t)k].status;
+  }
+  return 0;
+}
+int uvio_hp_debug_position_update_p(double *P, int N, int ld, int imu_id, const double *q, const double *p, int aux_id,
+                                    const double *s, int r, const double *C, const double *z, const double *R, int ldr,
+                                    double chi2_thr, double *dx, double *chi2, int *applied) {
+  try {
+    return Engine::position_update_standalone(P, N, ld, imu_id, q, p, aux_id, s, r, C, z, R, ldr, chi2_thr, dx, chi2,
+                                              applied);
+  } catch (const HpError &ex) {
+    return ex.code;
+  } catch (...) {
+    return UVIO_HP_E_DEVICE;
+  }
+}
+
 int uvio_hp_debug_last_msckf(uvio_hp_t *h, uint64_t *ids, double *pG, int *status, double *chi2, int cap, int *n) {
   if (!h || !n) return UVIO_HP_E_ARG;
   const auto &v = h->e->last_msckf_;

@@ -396,6 +396,10 @@ struct DeviceBufs {
   DevBuf<double> uwb_reg, uwb_h;
   PinBuf<double> uwb_host;
   size_t uwb_stride = 0;
+  // the chained position fixes of one timestamp (Engine::fix_update_chain) use the same regions and pinned mirror
+  // (kFixMaxChain <= kUwbMaxRanges; either chain ends in its own readback before the other can start) and one
+  // DFixRow per fix
+  DevBuf<DFixRow> fix_row;
   // Engine::marginal_cov: the gathered m x m block and its pinned mirror (both grow on demand)
   DevBuf<double> marg;
   PinBuf<double> marg_host;
@@ -479,6 +483,15 @@ class Engine {
   int feed_camera(double t, int ncam, const int *cam_ids, const uint8_t *const *imgs, const int *strides,
                   const uint8_t *const *masks, bool device_imgs);
   int feed_uwb(double t, int n, const uint64_t *ids, const double *ranges);
+  // uvio_hp_feed_position: one position fix into past_fix_, replayed inside the next frame (after_tracking)
+  int feed_position(double t, int r, const double *C, const double *z, const double *R, int ldr, const double *p_SinI,
+                    int aux_handle, double chi2_mult, int *queued);
+  // the fixes the last camera / simulation feed consumed, in processing order
+  struct FixResult {
+    double t, chi2;
+    int status;  // 0 applied, 1 gated, 2 dropped, 3 refused
+  };
+  const std::vector<FixResult> &position_results() const { return fix_results_; }
   Tracker *tracker() { return tracker_.get(); }
   int init_anchors(int n, const uvio_hp_anchor_t *a);
   // HIP's current device is per host thread: every C-ABI entry binds the engine's device first, so a handle
@@ -525,6 +538,11 @@ class Engine {
                                  int ldhx, const double *H_auxinv, const double *R, int ldr);
   static int aux_walk_standalone(double *P, int N, int ld, int ntab, const int *ids, const int *dims,
                                  const double *sigma2, double dt);
+  // the three kernels of the position-fix chain on a caller's host covariance (uvio_hp_debug_position_update_p)
+  static int position_update_standalone(double *P, int N, int ld, int imu_id, const double *q, const double *p,
+                                        int aux_id, const double *s, int r, const double *C, const double *z,
+                                        const double *R, int ldr, double chi2_thr, double *dx, double *chi2,
+                                        int *applied);
 
  private:
   uvio_hp_options_t o_;
@@ -609,6 +627,18 @@ class Engine {
   double startup_time_ = -1, distance_ = 0, timelastupdate_ = -1;
   bool anchors_initialized_ = false;
   std::map<double, std::unordered_map<size_t, double>> past_uwb_;
+  // the buffered position fixes by time, each time's in feed order (at most kFixQueueMax in all, fix_queued_);
+  // after_tracking merges them with past_uwb_ in ascending time
+  struct FixMeas {
+    int r;
+    double C[9], z[3], R[9];  // C: r x 3; R: r x r at leading dimension 3, symmetric
+    double s[3];              // the constant lever arm (aux <= 0)
+    int aux;                  // aux handle, <= 0: constant lever arm
+    double thr;
+  };
+  std::map<double, std::vector<FixMeas>> past_fix_;
+  int fix_queued_ = 0;
+  std::vector<FixResult> fix_results_;
   uvio_hp_timing_t timing_{};
   std::vector<double> chi2_table_;
   ShardComm shard_;
@@ -865,6 +895,9 @@ class Engine {
   // UpdaterUWB::update_single for every range of one UwbData message whose anchor is known, in the message's
   // order, as one device chain with one readback; returns the number of applied updates
   int uwb_update_message(const std::vector<std::pair<size_t, double>> &ranges);
+  // The fixes of one timestamp on the current state as device chains of up to kFixMaxChain fixes, one readback each:
+  // an aux lever arm's covariance offset and value are resolved here; one FixResult per fix is appended
+  void fix_update_chain(double t, const std::vector<FixMeas> &fixes);
   void marginalize_slam();
   void marginalize_old_clone();
   void db_update(size_t id, double t, size_t cam, float u, float v, float un, float vn);

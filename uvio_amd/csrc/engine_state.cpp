@@ -289,6 +289,8 @@ void Engine::alloc_device() {
   d_.uwb_reg = DevBuf<double>(kUwbMaxRanges * d_.uwb_stride);
   d_.uwb_h = DevBuf<double>(kUwbMaxRanges * 16);
   d_.uwb_host = PinBuf<double>(kUwbMaxRanges * d_.uwb_stride);
+  static_assert(kFixMaxChain <= kUwbMaxRanges, "the position-fix chain uses the UWB chain's regions");
+  d_.fix_row = DevBuf<DFixRow>(kFixMaxChain);
 }
 
 void Engine::upload_P_full(const std::vector<double> &Ph, int N) {
@@ -1105,6 +1107,57 @@ int Engine::aux_walk_standalone(double *P, int N, int ld, int ntab, const int *i
     HP_HIP(hipMemcpyAsync(dI, cidx.data(), sizeof(int) * m, hipMemcpyHostToDevice, s));
     launch_aux_walk(s, dP, ld, dI, ds2, m, dt);
   });
+}
+
+// One position fix through k_fix_rows -> k_fix_M -> k_fix_update (Engine::fix_update_chain's launches for a chain of
+// one) on a caller's covariance at a caller's pose
+int Engine::position_update_standalone(double *P, int N, int ld, int imu_id, const double *q, const double *p,
+                                       int aux_id, const double *s, int r, const double *C, const double *z,
+                                       const double *R, int ldr, double chi2_thr, double *dx, double *chi2,
+                                       int *applied) {
+  if (!P || !q || !p || !s || !C || !z || !R || !dx || !chi2 || !applied) return UVIO_HP_E_ARG;
+  if (r < 1 || r > 3 || ldr < r || N < 6 || ld < N || !(chi2_thr > 0.0)) return UVIO_HP_E_ARG;
+  if (imu_id < 0 || (long long)imu_id + 6 > N) return UVIO_HP_E_ARG;
+  if (aux_id >= 0 && ((long long)aux_id + 3 > N || (aux_id + 3 > imu_id && aux_id < imu_id + 6))) return UVIO_HP_E_ARG;
+  if (!aux_upper_ok(R, ldr, r, true)) return UVIO_HP_E_ARG;
+  DFixState st{};
+  bool finite = true;
+  for (int k = 0; k < 4; k++) finite = finite && std::isfinite(st.q[k] = q[k]);
+  for (int k = 0; k < 3; k++) finite = finite && std::isfinite(st.p[k] = p[k]) && std::isfinite(st.s[0][k] = s[k]);
+  for (int i = 0; i < r; i++) {
+    for (int k = 0; k < 3; k++) finite = finite && std::isfinite(st.C[0][3 * i + k] = C[3 * i + k]);
+    finite = finite && std::isfinite(st.z[0][i] = z[i]);
+    for (int j = i; j < r; j++) st.R[0][3 * i + j] = st.R[0][3 * j + i] = R[(size_t)i * ldr + j];
+  }
+  if (!finite) return UVIO_HP_E_ARG;
+  st.thr[0] = chi2_thr;
+  st.r[0] = r;
+  st.id_aux[0] = aux_id >= 0 ? aux_id : -1;
+  st.id_imu = imu_id;
+  st.nf = 1;
+  DevBuf<DFixState> dst;
+  DevBuf<DFixRow> drow;
+  DevBuf<double> dM, dreg;
+  std::vector<double> reg((size_t)N + 4, 0.0);
+  const int rc = aux_standalone_run(P, (size_t)N, ld, [&](hipStream_t sm, double *dP) {
+    dst = DevBuf<DFixState>(1);
+    drow = DevBuf<DFixRow>(1);
+    dM = DevBuf<double>((size_t)3 * N);
+    dreg = DevBuf<double>(reg.size());
+    HP_HIP(hipMemcpyAsync(dst, &st, sizeof(st), hipMemcpyHostToDevice, sm));
+    HP_HIP(hipMemsetAsync(dreg, 0, sizeof(double) * reg.size(), sm));
+    launch_fix_rows(sm, dst, 0, nullptr, drow, dreg);
+    launch_fix_M(sm, dP, ld, N, drow, r, dM);
+    launch_fix_update(sm, dP, ld, N, dM, drow, r, dreg);
+    HP_HIP(hipMemcpyAsync(reg.data(), dreg, sizeof(double) * reg.size(), hipMemcpyDeviceToHost, sm));
+  });
+  if (rc) return rc;
+  *chi2 = reg[2];
+  *applied = reg[0] != 0.0 ? 1 : 0;
+  for (int i = 0; i < N; i++) dx[i] = *applied ? reg[(size_t)4 + i] : 0.0;
+  if (reg[3] != 0.0) return UVIO_HP_E_ARG;  // S is not positive definite: nothing was applied
+  if (*applied && *reinterpret_cast<const int *>(&reg[1]) > 0) return UVIO_HP_E_NUMERIC;
+  return 0;
 }
 
 }  // namespace uvhp

@@ -145,6 +145,48 @@ int Engine::feed_uwb(double t, int n, const uint64_t *ids, const double *ranges)
   return 0;
 }
 
+// A position fix z = C (p_IinG + R_GtoI^T s) + noise(R) for the next frame's replay (after_tracking), buffered the
+// way feed_uwb buffers a message.  Every refusal comes before anything is stored.
+int Engine::feed_position(double t, int r, const double *C, const double *z, const double *R, int ldr,
+                          const double *p_SinI, int aux_handle, double chi2_mult, int *queued) {
+  stage_ = "feed_position";
+  const char *who = "feed_position: ";
+  if (!C || !z || !R || !queued || (aux_handle <= 0 && !p_SinI)) throw HpError(UVIO_HP_E_ARG, std::string(who) + "null pointer");
+  *queued = 0;
+  if (r < 1 || r > 3) throw HpError(UVIO_HP_E_ARG, std::string(who) + "r outside 1 .. 3");
+  if (ldr < r) throw HpError(UVIO_HP_E_ARG, std::string(who) + "leading dimension below the row length");
+  if (!(chi2_mult > 0.0)) throw HpError(UVIO_HP_E_ARG, std::string(who) + "chi2_mult must be positive");
+  FixMeas m{};
+  bool finite = std::isfinite(t);
+  for (int i = 0; i < r; i++) {
+    for (int k = 0; k < 3; k++) finite = finite && std::isfinite(m.C[3 * i + k] = C[3 * i + k]);
+    finite = finite && std::isfinite(m.z[i] = z[i]);
+    for (int j = i; j < r; j++) finite = finite && std::isfinite(m.R[3 * i + j] = m.R[3 * j + i] = R[(size_t)i * ldr + j]);
+  }
+  if (aux_handle <= 0)
+    for (int k = 0; k < 3; k++) finite = finite && std::isfinite(m.s[k] = p_SinI[k]);
+  if (!finite)
+    throw HpError(UVIO_HP_E_ARG, std::string(who) + "t, C, z, the upper triangle of R or p_SinI is not finite");
+  for (int i = 0; i < r; i++)
+    if (!(m.R[4 * i] > 0.0)) throw HpError(UVIO_HP_E_ARG, std::string(who) + "the diagonal of R must be positive");
+  // feed_uwb's behaviour (UVioManager.cpp:61-79): nothing is kept before initialization or at a time the state has passed
+  if (!is_initialized_ || timestamp_ >= t) return 0;
+  if (aux_handle > 0) {
+    auto it = aux_.find(aux_handle);
+    if (it == aux_.end()) throw HpError(UVIO_HP_E_ARG, std::string(who) + "no live aux variable has this handle");
+    if (it->second.v->size != 3) throw HpError(UVIO_HP_E_ARG, std::string(who) + "the aux variable is not a 3-vector");
+  }
+  if (fix_queued_ >= kFixQueueMax)
+    throw HpError(UVIO_HP_E_CAPACITY, std::string(who) + "more than " + std::to_string(kFixQueueMax) + " fixes queued");
+  m.r = r;
+  m.aux = aux_handle > 0 ? aux_handle : 0;
+  m.thr = chi2_mult * chi2_table_[r];
+  past_fix_[t].push_back(m);
+  fix_queued_++;
+  *queued = 1;
+  return 0;
+}
+
 // UVioManager.cpp:81-113 / 207-266
 int Engine::init_anchors(int n, const uvio_hp_anchor_t *a) {
   if (n <= 0) return 0;
@@ -371,6 +413,8 @@ bool Engine::propagation_can_precede_tracking(double t) const {
   if (o_.try_zupt && (!o_.zupt_only_at_beginning || !has_moved_since_zupt_)) return false;
   for (auto it = past_uwb_.begin(); it != past_uwb_.end() && it->first < t; it++)
     if (it->first > timestamp_) return false;
+  for (auto it = past_fix_.begin(); it != past_fix_.end() && it->first < t; it++)
+    if (it->first > timestamp_) return false;
   return true;
 }
 
@@ -380,6 +424,7 @@ int Engine::after_tracking(double t, const std::vector<int> &camids, clk::time_p
   auto rT2 = clk::now();
   timing_ = uvio_hp_timing_t{};
   frame_feats_.clear();
+  fix_results_.clear();
   timing_.tracking = secs(rT1, rT2) - early_prop_s_;
   timing_.device_syncs = track_syncs;
   timing_.sync_wait = track_wait;
@@ -420,26 +465,56 @@ int Engine::after_tracking(double t, const std::vector<int> &camids, clk::time_p
       return 0;
     }
   }
-  if (!past_uwb_.empty()) {
+  // The buffered UWB messages (UVioManager.cpp:178-188) and position fixes of (timestamp_, t) in ONE pass in
+  // ascending time: propagate to each distinct time, then that time's chain; at equal times the UWB message goes
+  // first, then the fixes in feed order.  A fix at the frame time is dropped (the UWB loop's it->first < t), and so is
+  // one the state has already passed (a caller's uvio_hp_propagate overtook it).
+  if (!past_uwb_.empty() || !past_fix_.empty()) {
     HPROF("uwb");
-    for (auto it = past_uwb_.begin(); it != past_uwb_.lower_bound(t); it++) {
-      if (it->first < t && it->first > timestamp_) {
-        bool valid = false;
-        for (auto &r : it->second)
-          if (anchors_.count(r.first)) valid = true;
-        if (!valid) continue;
-        {
-          HPROF("uwb.prop");
-          if (propagate_uwb(it->first) != 0) continue;
+    auto u = past_uwb_.begin();
+    const auto ue = past_uwb_.lower_bound(t);
+    auto f = past_fix_.begin();
+    const auto fe = past_fix_.upper_bound(t);
+    double reached = -INFINITY;  // the time this pass has propagated the state to
+    while (u != ue || f != fe) {
+      if (u != ue && (f == fe || u->first <= f->first)) {
+        const auto it = u++;
+        if (it->first < t && it->first > timestamp_) {
+          bool valid = false;
+          for (auto &r : it->second)
+            if (anchors_.count(r.first)) valid = true;
+          if (!valid) continue;
+          {
+            HPROF("uwb.prop");
+            if (propagate_uwb(it->first) != 0) continue;
+          }
+          reached = it->first;
+          HPROF("uwb.chain");
+          std::vector<std::pair<size_t, double>> rs;
+          for (auto &r : it->second)
+            if (anchors_.count(r.first)) rs.emplace_back(r.first, r.second);
+          uwb_update_message(rs);
         }
-        HPROF("uwb.chain");
-        std::vector<std::pair<size_t, double>> rs;
-        for (auto &r : it->second)
-          if (anchors_.count(r.first)) rs.emplace_back(r.first, r.second);
-        uwb_update_message(rs);
+        continue;
       }
+      const auto it = f++;
+      const double tf = it->first;
+      bool run = tf < t && (tf > timestamp_ || (tf == timestamp_ && tf == reached));
+      if (run && tf > timestamp_) {
+        HPROF("fix.prop");
+        run = propagate_uwb(tf) == 0;
+        if (run) reached = tf;
+      }
+      if (!run) {
+        for (size_t k = 0; k < it->second.size(); k++) fix_results_.push_back(FixResult{tf, 0.0, 2});
+        continue;
+      }
+      HPROF("fix.chain");
+      fix_update_chain(tf, it->second);
     }
     past_uwb_.erase(past_uwb_.begin(), past_uwb_.upper_bound(t));
+    for (auto it = past_fix_.begin(); it != fe; it++) fix_queued_ -= (int)it->second.size();
+    past_fix_.erase(past_fix_.begin(), fe);
   }
   int rc = do_feature_propagate_update(t, camids, rT2);
   if (rc == 0) odom_flush();  // the frame's snapshot for the IMU-rate odometry, if its update stage ran
@@ -1316,6 +1391,79 @@ int Engine::uwb_update_message(const std::vector<std::pair<size_t, double>> &ran
     }
   }
   return applied;
+}
+
+// The position fixes of one timestamp as device chains shaped like uwb_update_message's: the linearization state
+// (IMU pose, every fix's lever arm) goes up once per chain; per fix k_fix_rows moves it by the previous fix's dx when
+// that was accepted and forms H and the residual, k_fix_M forms M = P[:, I] H^T, k_fix_update factors S, gates chi2 on
+// the device and updates P and dx when accepted.  One readback returns every fix's
+// [accepted, negative diagonals, chi2, refused | dx]; the host then applies the accepted dx's to its mean in order.
+// An aux lever arm is looked up here, at replay: its covariance offset moves when clones in front of it are
+// marginalized, and a handle removed since the feed refuses its fix (status 3) without touching the state.
+void Engine::fix_update_chain(double t, const std::vector<FixMeas> &fixes) {
+  stage_ = "position fix chain";
+  std::vector<const FixMeas *> live;
+  std::vector<size_t> slot;  // live fix -> its entry of fix_results_
+  for (const FixMeas &m : fixes) {
+    fix_results_.push_back(FixResult{t, 0.0, 3});
+    if (m.aux > 0) {
+      auto it = aux_.find(m.aux);
+      if (it == aux_.end() || it->second.v->size != 3) continue;
+    }
+    live.push_back(&m);
+    slot.push_back(fix_results_.size() - 1);
+  }
+  for (size_t c0 = 0; c0 < live.size(); c0 += kFixMaxChain) {
+    const int nf = (int)std::min(live.size() - c0, (size_t)kFixMaxChain);
+    DFixState st{};
+    std::memcpy(st.q, imu_->val, sizeof(double) * 4);
+    std::memcpy(st.p, imu_->val + 4, sizeof(double) * 3);
+    st.id_imu = imu_->id;
+    st.nf = nf;
+    for (int j = 0; j < nf; j++) {
+      const FixMeas &m = *live[c0 + j];
+      const Var *av = m.aux > 0 ? aux_.at(m.aux).v.get() : nullptr;
+      std::memcpy(st.s[j], av ? av->val : m.s, sizeof(double) * 3);
+      std::memcpy(st.C[j], m.C, sizeof(m.C));
+      std::memcpy(st.z[j], m.z, sizeof(m.z));
+      std::memcpy(st.R[j], m.R, sizeof(m.R));
+      st.thr[j] = m.thr;
+      st.r[j] = m.r;
+      st.id_aux[j] = av ? av->id : -1;
+    }
+    DFixState *dst = stage(&st, 1);
+    stage_flush();
+    for (int j = 0; j < nf; j++) {
+      double *reg = d_.uwb_reg + (size_t)j * d_.uwb_stride;
+      const DFixRow *row = d_.fix_row + j;
+      launch_fix_rows(d_.stream, dst, j, j ? reg - d_.uwb_stride : nullptr, d_.fix_row + j, reg);
+      launch_fix_M(d_.stream, d_.P, d_.ldp, N_, row, st.r[j], d_.ekf.M);
+      launch_fix_update(d_.stream, d_.P, d_.ldp, N_, d_.ekf.M, row, st.r[j], reg);
+    }
+    ++p_epoch_;
+    const size_t n = (size_t)(nf - 1) * d_.uwb_stride + 4 + N_;
+    HP_HIP(hipMemcpyAsync(d_.uwb_host, d_.uwb_reg, sizeof(double) * n, hipMemcpyDeviceToHost, d_.stream));
+    dev_sync();
+    bool applied = false;
+    for (int j = 0; j < nf; j++) {
+      const double *reg = d_.uwb_host + (size_t)j * d_.uwb_stride;
+      FixResult &res = fix_results_[slot[c0 + j]];
+      res.chi2 = reg[2];
+      if (reg[0] == 0.0) {
+        res.status = reg[3] != 0.0 ? 3 : 1;
+        continue;
+      }
+      if (*reinterpret_cast<const int *>(reg + 1) > 0)
+        throw HpError(UVIO_HP_E_NUMERIC, "position fix EKFUpdate: negative covariance diagonal");
+      apply_dx(reg + 4);
+      res.status = 0;
+      applied = true;
+    }
+    if (applied) {  // as after an applied uvio_hp_measurement_update
+      odom_invalidate();
+      odom_flush();
+    }
+  }
 }
 
 }  // namespace uvhp

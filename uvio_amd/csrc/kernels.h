@@ -232,6 +232,44 @@ void launch_uwb_M(hipStream_t s, const double *P, int ldp, int N, const double *
 void launch_uwb_update(hipStream_t s, double *P, int ldp, int N, const double *M, const double *h, const int *hidx,
                        int n, double s2, double thr, double *region);
 
+// Buffered position fixes (include/uvio_hp.h uvio_hp_feed_position; Engine::fix_update_chain): the fixes that share
+// one timestamp as one device chain shaped like the UWB one.  z = C (p_IinG + R_GtoI^T s) + noise(R), r = 1 .. 3 rows,
+// s a constant lever arm or a live 3-dimensional aux variable; H over the error state is
+// C [-R_GtoI^T [s]x | I | R_GtoI^T], the last block only for an aux lever arm (JPL left error).
+constexpr int kFixMaxChain = 8;    // fixes of one chain (one readback); more at one timestamp run as several chains
+constexpr int kFixQueueMax = 256;  // fixes the host queue holds (UVIO_HP_E_CAPACITY beyond)
+struct DFixState {
+  double q[4], p[3];              // IMU q_GtoI, p_IinG: the chain's linearization state
+  double s[kFixMaxChain][3];      // fix j's lever arm (an aux one moves with every accepted dx)
+  double C[kFixMaxChain][9];      // r x 3 row-major in the first 3 r entries
+  double z[kFixMaxChain][3];
+  double R[kFixMaxChain][9];      // r x r at leading dimension 3, symmetric (mirrored from the upper triangle)
+  double thr[kFixMaxChain];       // chi2 threshold (INFINITY: no gate)
+  int r[kFixMaxChain];
+  int id_aux[kFixMaxChain];       // covariance id of the aux lever arm, < 0: constant
+  int id_imu, nf;
+};
+// what k_fix_rows leaves for the other two kernels of fix j
+struct DFixRow {
+  double H[3][9];   // r x n, n = 6 or 9
+  double res[3];    // z - C pred
+  double R[9];      // leading dimension 3
+  double thr;
+  int hidx[9];      // covariance index of H's column k
+  int n, pad;
+};
+// fix j: move the linearization state by fix j-1's dx if that was accepted (prev: its region, null for j = 0), form
+// the row block and zero the region's header [accepted, negative diagonals (int) | halt (int), chi2, refused];
+// a negative diagonal or a halt in prev halts this fix too
+void launch_fix_rows(hipStream_t s, DFixState *st, int j, const double *prev, DFixRow *row, double *region);
+// M = P[:, hidx] H^T as r column arrays of length N (column c at M + c N)
+void launch_fix_M(hipStream_t s, const double *P, int ldp, int N, const DFixRow *row, int r, double *M);
+// S = H M[hidx, :] + R = L L^T in registers (a pivot that is not finite or not positive, or a NaN chi2: refused),
+// chi2 = |L^-1 res|^2 against row->thr; accepted: P -= W W^T (W = M L^-T), dx = W L^-1 res.
+// region: [accepted, negative diagonals (int) | halt (int), chi2, refused | dx (N)]
+void launch_fix_update(hipStream_t s, double *P, int ldp, int N, const double *M, const DFixRow *row, int r,
+                       double *region);
+
 struct EkfScratch {
   double *M, *W, *S, *y, *dx;
   int *neg;

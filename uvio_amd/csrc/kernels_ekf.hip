@@ -488,6 +488,188 @@ void launch_uwb_update(hipStream_t s, double *P, int ldp, int N, const double *M
                      nb);
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Chained position fixes (kernels.h DFixState): the UWB chain's three steps for an r-row measurement, r = 1 .. 3
+__global__ void k_fix_rows(DFixState *st, int j, const double *__restrict__ prev, DFixRow *__restrict__ row,
+                           double *__restrict__ region) {
+  if (threadIdx.x != 0) return;
+  DFixState &u = *st;
+  // a negative covariance diagonal in an earlier fix of the chain halts the rest of it, as in k_uwb_row
+  bool halt = false;
+  if (prev) {
+    const int *pi = reinterpret_cast<const int *>(prev + 1);
+    halt = pi[0] > 0 || pi[1] != 0;
+    if (prev[0] != 0.0 && !halt) {
+      // Var::update of the previous fix's dx: IMU quaternion boxplus + position, the aux lever arms additive
+      const double *dx = prev + 4;
+      quat_boxplus(u.q, dx + u.id_imu);
+      for (int k = 0; k < 3; k++) u.p[k] += dx[u.id_imu + 3 + k];
+      for (int a = 0; a < u.nf; a++)
+        if (u.id_aux[a] >= 0)
+          for (int k = 0; k < 3; k++) u.s[a][k] += dx[u.id_aux[a] + k];
+    }
+  }
+  const int r = u.r[j];
+  const bool aux = u.id_aux[j] >= 0;
+  const double *s = u.s[j], *C = u.C[j];
+  double Rm[9], Sx[9], A[9], pred[3];
+  quat_2_Rot(u.q, Rm);   // R_GtoI
+  m3t_vec(Rm, s, pred);  // R_GtoI^T s
+  for (int k = 0; k < 3; k++) pred[k] += u.p[k];
+  skew(s, Sx);
+  m3_mul_at(Rm, Sx, A);  // R_GtoI^T [s]x
+  DFixRow &o = *row;
+  for (int a = 0; a < 3; a++) {
+    for (int k = 0; k < 9; k++) o.H[a][k] = 0.0;
+    o.res[a] = 0.0;
+    if (a >= r) continue;
+    const double *c = C + 3 * a;
+    for (int k = 0; k < 3; k++) {
+      o.H[a][k] = -(c[0] * A[k] + c[1] * A[3 + k] + c[2] * A[6 + k]);
+      o.H[a][3 + k] = c[k];
+      if (aux) o.H[a][6 + k] = c[0] * Rm[3 * k] + c[1] * Rm[3 * k + 1] + c[2] * Rm[3 * k + 2];
+    }
+    o.res[a] = u.z[j][a] - dot3(c, pred);
+  }
+  for (int k = 0; k < 9; k++) {
+    o.R[k] = u.R[j][k];
+    o.hidx[k] = k < 6 ? u.id_imu + k : (aux ? u.id_aux[j] + k - 6 : 0);
+  }
+  o.thr = u.thr[j];
+  o.n = aux ? 9 : 6;
+  o.pad = 0;
+  region[0] = 0.0;
+  region[1] = 0.0;  // the negative-diagonal count (int bits, low word) and the halt flag (high word)
+  if (halt) reinterpret_cast<int *>(region + 1)[1] = 1;
+  region[2] = region[3] = 0.0;
+}
+
+void launch_fix_rows(hipStream_t s, DFixState *st, int j, const double *prev, DFixRow *row, double *region) {
+  hipLaunchKernelGGL(k_fix_rows, dim3(1), dim3(64), 0, s, st, j, prev, row, region);
+}
+
+template <int R>
+__global__ void __launch_bounds__(256) k_fix_M(const double *__restrict__ P, int ldp, int N,
+                                               const DFixRow *__restrict__ row, double *__restrict__ M) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const double *Pr = P + (size_t)i * ldp;
+  const int n = row->n;
+  double a[R];
+#pragma unroll
+  for (int c = 0; c < R; c++) a[c] = 0.0;
+  for (int k = 0; k < n; k++) {
+    const double pv = Pr[row->hidx[k]];
+#pragma unroll
+    for (int c = 0; c < R; c++) a[c] = fma(pv, row->H[c][k], a[c]);
+  }
+#pragma unroll
+  for (int c = 0; c < R; c++) M[(size_t)c * N + i] = a[c];
+}
+
+void launch_fix_M(hipStream_t s, const double *P, int ldp, int N, const DFixRow *row, int r, double *M) {
+  if (r < 1 || r > 3) throw std::runtime_error("position fix: " + std::to_string(r) + " rows");
+  auto *k = r == 1 ? k_fix_M<1> : r == 2 ? k_fix_M<2> : k_fix_M<3>;
+  hipLaunchKernelGGL(k, dim3((N + 255) / 256), dim3(256), 0, s, P, ldp, N, row, M);
+}
+
+// tile pair (bi, bj), bi <= bj, of the 16 x 16 tiles of P, one element per thread (k_uwb_update's mapping)
+template <int R>
+__global__ void __launch_bounds__(256) k_fix_update(double *__restrict__ P, int ldp, int N, const double *__restrict__ M,
+                                                    const DFixRow *__restrict__ row, double *__restrict__ region,
+                                                    int nb) {
+  if (reinterpret_cast<const int *>(region + 1)[1] != 0) return;  // halted (k_fix_rows): not applied, region[0] = 0
+  // the innovation covariance, its factor and the gate, the same arithmetic in every block
+  const int n = row->n;
+  double S[R][R], L[R][R], y[R];
+#pragma unroll
+  for (int a = 0; a < R; a++)
+#pragma unroll
+    for (int b = a; b < R; b++) {
+      double acc = 0.0;
+      for (int k = 0; k < n; k++) acc = fma(row->H[a][k], M[(size_t)b * N + row->hidx[k]], acc);
+      S[a][b] = acc + row->R[3 * a + b];
+    }
+  bool bad = false;
+#pragma unroll
+  for (int j = 0; j < R; j++) {
+    double d = S[j][j];
+#pragma unroll
+    for (int k = 0; k < j; k++) d -= L[j][k] * L[j][k];
+    if (!(isfinite(d) && d > 0.0)) bad = true;
+    L[j][j] = sqrt(d);
+#pragma unroll
+    for (int i = j + 1; i < R; i++) {
+      double v = S[j][i];
+#pragma unroll
+      for (int k = 0; k < j; k++) v -= L[i][k] * L[j][k];
+      L[i][j] = v / L[j][j];
+    }
+  }
+  double chi2 = 0.0;
+#pragma unroll
+  for (int i = 0; i < R; i++) {
+    double v = row->res[i];
+#pragma unroll
+    for (int k = 0; k < i; k++) v -= L[i][k] * y[k];
+    y[i] = v / L[i][i];
+    chi2 += y[i] * y[i];
+  }
+  const bool refused = bad || chi2 != chi2;
+  const bool acc = !refused && !(chi2 > row->thr);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    region[0] = acc ? 1.0 : 0.0;
+    region[2] = bad ? __builtin_nan("") : chi2;
+    region[3] = refused ? 1.0 : 0.0;
+  }
+  if (!acc) return;
+  int b = blockIdx.x, bi = 0;
+  while (b >= nb - bi) {
+    b -= nb - bi;
+    bi++;
+  }
+  const int bj = bi + b;
+  const int ei = threadIdx.x >> 4, ej = threadIdx.x & 15;
+  const int gi = 16 * bi + ei, gj = 16 * bj + ej;
+  if (gi >= N || gj >= N) return;
+  // rows gi and gj of W = M L^-T: L w^T = m^T by forward substitution
+  double wi[R], wj[R];
+#pragma unroll
+  for (int c = 0; c < R; c++) {
+    double vi = M[(size_t)c * N + gi], vj = M[(size_t)c * N + gj];
+#pragma unroll
+    for (int k = 0; k < c; k++) {
+      vi -= L[c][k] * wi[k];
+      vj -= L[c][k] * wj[k];
+    }
+    wi[c] = vi / L[c][c];
+    wj[c] = vj / L[c][c];
+  }
+  if (bi < bj || ej >= ei) {
+    double ww = 0.0;
+#pragma unroll
+    for (int c = 0; c < R; c++) ww += wi[c] * wj[c];
+    const double v = P[(size_t)gi * ldp + gj] - ww;
+    P[(size_t)gi * ldp + gj] = v;
+    P[(size_t)gj * ldp + gi] = v;
+    if (gi == gj && v < 0.0) atomicAdd(reinterpret_cast<int *>(region + 1), 1);
+  }
+  if (bi == bj && ei == 0) {
+    double d = 0.0;
+#pragma unroll
+    for (int c = 0; c < R; c++) d += wj[c] * y[c];
+    region[4 + gj] = d;
+  }
+}
+
+void launch_fix_update(hipStream_t s, double *P, int ldp, int N, const double *M, const DFixRow *row, int r,
+                       double *region) {
+  if (r < 1 || r > 3) throw std::runtime_error("position fix: " + std::to_string(r) + " rows");
+  const int nb = (N + 15) / 16;
+  auto *k = r == 1 ? k_fix_update<1> : r == 2 ? k_fix_update<2> : k_fix_update<3>;
+  hipLaunchKernelGGL(k, dim3(nb * (nb + 1) / 2), dim3(256), 0, s, P, ldp, N, M, row, region, nb);
+}
+
 static void ensure_ekf_lds_attrs() {
   static bool done = false;
   if (done) return;

@@ -435,6 +435,41 @@ class VioManager:
         return self.measurement_update([(int(imu[1]), 6), (aid, 3)], H, np.asarray(p_meas, dtype=np.float64) - pred, R,
                                        chi2_mult * chi2_95(3))
 
+    # ---- buffered position fixes (uvio_hp_feed_position): replayed in time order inside the next frame ----
+    def feed_measurement_position(self, t, z, R, Cm=None, p_SinI=None, aux_handle=0, chi2_mult=1.0):
+        """Queue the fix z = Cm (p_IinG + R_GtoI^T s) + noise(R) at time t: Cm (r, 3), r = 1 .. 3 (None: the identity),
+        R (r, r) with its upper triangle read, s the constant lever arm p_SinI (None: zero) or, with aux_handle > 0, a
+        3-dimensional variable of add_state.  Gated at chi2_mult * chi2_95(r) (inf: no gate).  The next camera or
+        simulation feed propagates to t and applies it, merged in time order with the UWB messages.  Returns True when
+        the fix was queued, False when the filter is not initialized or t is not after the state time."""
+        z = np.ascontiguousarray(z, dtype=np.float64).reshape(-1)
+        r = z.size
+        if Cm is None and r != 3:
+            raise ValueError("feed_measurement_position: a fix of %d rows needs its Cm" % r)
+        Cm = np.ascontiguousarray(np.eye(3) if Cm is None else np.asarray(Cm, dtype=np.float64).reshape(r, 3))
+        R = np.ascontiguousarray(np.asarray(R, dtype=np.float64).reshape(r, r))
+        s = None
+        if int(aux_handle) <= 0:
+            s = np.ascontiguousarray(np.zeros(3) if p_SinI is None else p_SinI, dtype=np.float64).reshape(3)
+        queued = C.c_int(0)
+        self._check(self._call("feed_position", self._h, C.c_double(t), r, _dp(Cm), _dp(z), _dp(R), max(r, 1),
+                               None if s is None else _dp(s), int(aux_handle), C.c_double(chi2_mult),
+                               C.byref(queued)), "feed_measurement_position")
+        return bool(queued.value)
+
+    def position_results(self):
+        """The fixes the last camera or simulation feed consumed, in processing order: a list of
+        {"t", "chi2", "status"}; status 0 applied, 1 gated, 2 dropped, 3 refused."""
+        n = C.c_int(0)
+        rc = self._call("get_position_results", self._h, None, None, None, 0, C.byref(n))
+        if rc != N.E_CAPACITY:
+            self._check(rc, "get_position_results")
+        k = n.value
+        t, chi2, st = np.zeros(max(k, 1)), np.zeros(max(k, 1)), np.zeros(max(k, 1), dtype=np.int32)
+        self._check(self._call("get_position_results", self._h, _dp(t), _dp(chi2), st.ctypes.data_as(C.POINTER(C.c_int)),
+                               k, C.byref(n)), "get_position_results")
+        return [{"t": float(t[i]), "chi2": float(chi2[i]), "status": int(st[i])} for i in range(k)]
+
     # ---- getters ----
     def initialized(self):
         """VioManager::initialized (VioManager.h:99): initialize_with_gt ran or an initializer succeeded."""
@@ -870,6 +905,31 @@ def aux_walk_p(P, ids, dims, sigma2, dt, ld=None):
                                      float(dt))
     N.check(rc, what="uvio_hp_aux_walk_p")
     return buf
+
+
+def position_update_p(P, imu_id, q_GtoI, p_IinG, s, Cm, z, R, aux_id=-1, chi2_thr=float("inf"), ld=None):
+    """uvio_hp_debug_position_update_p: k_fix_rows -> k_fix_M -> k_fix_update for one fix on a standalone covariance at
+    the given pose.  The IMU pose's error columns start at imu_id, the lever arm s's at aux_id (< 0: a constant).
+    Cm (r, 3), z (r), R (r, r') with r' >= r its leading dimension.  Returns (buf, dx, chi2, applied): the (N, ld)
+    buffer as it came back (padding included); not applied: P unchanged, dx zeros."""
+    z = np.ascontiguousarray(z, dtype=np.float64).reshape(-1)
+    r = z.size
+    Cm = np.ascontiguousarray(np.asarray(Cm, dtype=np.float64).reshape(r, 3))
+    R = np.ascontiguousarray(R, dtype=np.float64)
+    q = np.ascontiguousarray(q_GtoI, dtype=np.float64).reshape(4)
+    p = np.ascontiguousarray(p_IinG, dtype=np.float64).reshape(3)
+    s = np.ascontiguousarray(s, dtype=np.float64).reshape(3)
+    Nn = np.shape(P)[0]
+    ld = Nn if ld is None else int(ld)
+    buf = _padded(P, Nn, ld)
+    dx = np.zeros(Nn)
+    chi2, applied = C.c_double(0.0), C.c_int(0)
+    lib = N.load()
+    rc = lib.uvio_hp_debug_position_update_p(_dp(buf), Nn, ld, int(imu_id), _dp(q), _dp(p), int(aux_id), _dp(s), r,
+                                             _dp(Cm), _dp(z), _dp(R), R.shape[1], float(chi2_thr), _dp(dx),
+                                             C.byref(chi2), C.byref(applied))
+    N.check(rc, what="uvio_hp_debug_position_update_p")
+    return buf, dx, chi2.value, bool(applied.value)
 
 
 def compress(A):
