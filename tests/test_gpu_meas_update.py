@@ -2,7 +2,7 @@
 covariance), uvio_hp_measurement_update and uvio_hp_propagate on a handle.
 
 1. Numerics: the dense-R update against the extended-precision reference (tests/meas_ref.py) at the dispatch
-   edges of k_ekf_fact_R<W, LDS> (meas_ref.SHAPES: panel waves 1 / 2 / 3 / 5, the factor in LDS up to r = 137 and in
+   edges of k_ekf_fact<W, LDS, true> (meas_ref.SHAPES: panel waves 1 / 2 / 3 / 5, the factor in LDS up to r = 137 and in
    global memory from 138, N around the 16-row tiles of P), R dense and graded over four orders of magnitude, no gate.
    P exactly symmetric, and in ekf_ref.scaled_err / scaled_dx_err units
        e_dev <= RATIO * max(e_f64, 16 * 2^-52)
@@ -84,7 +84,7 @@ def _direct(r):
 
 @pytest.mark.parametrize("c", [_direct(1), _direct(111), _direct(255)], ids=E.case_id)
 def test_isotropic_R_is_bit_identical_to_the_sigma2_update(c):
-    """k_ekf_MS with sigma2 = 0 leaves acc + 0.0 and k_ekf_fact_R adds R on top: (acc + 0.0) + sigma2 is the sum
+    """k_ekf_MS with sigma2 = 0 leaves acc + 0.0 and k_ekf_fact's dense-R instance adds R on top: (acc + 0.0) + sigma2 is the sum
     k_ekf_MS forms itself, so with no gate every later value is the same"""
     import uvio_amd as U
     k = E.graded_case(**c)

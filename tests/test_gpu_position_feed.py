@@ -1,5 +1,5 @@
 """Buffered position fixes on the device: uvio_hp_feed_position / uvio_hp_get_position_results on a handle and the
-chain's three kernels (k_fix_rows -> k_fix_M -> k_fix_update) on a standalone covariance
+chain's three kernels (k_fix_rows -> k_chain_M -> k_chain_update) on a standalone covariance
 (uvio_hp_debug_position_update_p).
 
 1. Numerics of the three kernels against the extended-precision reference (tests/fix_ref.py): N = 15, 16, 17, 33 (the

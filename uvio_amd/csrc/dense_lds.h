@@ -14,7 +14,21 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "hp_math.h"
+
 namespace uvhp {
+
+// Pair number b of the upper triangle of an n x n grid, enumerated row by row ((0,0) .. (0,n-1), (1,1) ..):
+// its row i and column j, i <= j.  The tile-pair decode of every kernel that takes one (bi <= bj) tile pair of a
+// symmetric matrix per workgroup or wave.
+HPD void upper_pair(int b, int n, int &i, int &j) {
+  i = 0;
+  while (b >= n - i) {
+    b -= n - i;
+    i++;
+  }
+  j = i + b;
+}
 
 // Stage `count` doubles: st(e, ld(e)) for e < count, with the global loads batched kStageBatch per
 // thread (issued together, so staging costs one memory round trip per batch instead of one per element).
@@ -705,12 +719,10 @@ __device__ __forceinline__ void ldl_wave_inv(double *A, LA la, int n, int nrows,
           }
           u -= nxo;
         }
-        int C = J + 1;
-        while (u >= nbr - C) {
-          u -= nbr - C;
-          C++;
-        }
-        const int I = C + u;
+        int C, I;  // the trailing tiles (C <= I) of block rows J + 1 .. nbr - 1
+        upper_pair(u, nbr - (J + 1), C, I);
+        C += J + 1;
+        I += J + 1;
         dbl4 acc = tile_load_lower(A, la, 16 * I, 16 * C, nrows, n, kq, r16);
         acc = tile_rank16(A, la, Dd, 16 * I, 16 * C, 16 * P, nrows, n, kq, r16, acc);
         tile_store_lower(A, la, 16 * I, 16 * C, nrows, n, kq, r16, acc);

@@ -391,15 +391,14 @@ struct DeviceBufs {
   int fout_cap = 0;            // per-feature result slots in fout / fout_host (one frame chain's batches)
   DevBuf<char> frame;          // the frame chain's device state: clone / camera tables, pose values, mirror
   size_t frame_bytes = 0;
-  // the chained UWB ranges of one message (Engine::uwb_update_message): per range a region [accepted, negative
-  // diagonals, chi2, S | dx] of uwb_stride doubles (pinned mirror uwb_host) and its row h (16 doubles)
-  DevBuf<double> uwb_reg, uwb_h;
-  PinBuf<double> uwb_host;
-  size_t uwb_stride = 0;
-  // the chained position fixes of one timestamp (Engine::fix_update_chain) use the same regions and pinned mirror
-  // (kFixMaxChain <= kUwbMaxRanges; either chain ends in its own readback before the other can start) and one
-  // DFixRow per fix
-  DevBuf<DFixRow> fix_row;
+  // the measurement chains (Engine::run_mchain: the UWB ranges of one message, the position fixes of one
+  // timestamp): per step a region (kernels.h DChainRegion, then dx) of mchain_stride doubles in raw device bytes
+  // (chain_region types them), the pinned mirror of all regions, and one DChainRow per step.  Either chain ends in
+  // its own readback before the other can start, so both use the same kChainMaxSteps slots.
+  DevBuf<unsigned char> mchain_reg;
+  PinBuf<double> mchain_host;
+  size_t mchain_stride = 0;
+  DevBuf<DChainRow> mchain_row;
   // Engine::marginal_cov: the gathered m x m block and its pinned mirror (both grow on demand)
   DevBuf<double> marg;
   PinBuf<double> marg_host;
@@ -898,6 +897,11 @@ class Engine {
   // The fixes of one timestamp on the current state as device chains of up to kFixMaxChain fixes, one readback each:
   // an aux lever arm's covariance offset and value are resolved here; one FixResult per fix is appended
   void fix_update_chain(double t, const std::vector<FixMeas> &fixes);
+  // One measurement chain of n <= kChainMaxSteps steps on d_.stream: enqueue(j, prev, row, region) puts step j's
+  // three launches there (prev: step j-1's region, null for j = 0).  Then one readback of every region and one
+  // wait; returns the pinned regions (step j's at j * d_.mchain_stride doubles: chain_header, then dx).
+  template <class F>
+  const double *run_mchain(int n, F &&enqueue);
   void marginalize_slam();
   void marginalize_old_clone();
   void db_update(size_t id, double t, size_t cam, float u, float v, float un, float vn);

@@ -285,12 +285,10 @@ void Engine::alloc_device() {
   if (const char *e = std::getenv("UVIO_HP_NO_PREDETECT")) predetect_on_ = e[0] != '1';
   d_.stg_h = PinBuf<char>(d_.stg_cap);
   d_.stg_d = DevBuf<char>(d_.stg_cap);
-  d_.uwb_stride = (size_t)d_.ldp + 4;
-  d_.uwb_reg = DevBuf<double>(kUwbMaxRanges * d_.uwb_stride);
-  d_.uwb_h = DevBuf<double>(kUwbMaxRanges * 16);
-  d_.uwb_host = PinBuf<double>(kUwbMaxRanges * d_.uwb_stride);
-  static_assert(kFixMaxChain <= kUwbMaxRanges, "the position-fix chain uses the UWB chain's regions");
-  d_.fix_row = DevBuf<DFixRow>(kFixMaxChain);
+  d_.mchain_stride = (size_t)d_.ldp + kChainHeader;
+  d_.mchain_reg = DevBuf<unsigned char>(kChainMaxSteps * d_.mchain_stride * sizeof(double));
+  d_.mchain_host = PinBuf<double>(kChainMaxSteps * d_.mchain_stride);
+  d_.mchain_row = DevBuf<DChainRow>(kChainMaxSteps);
 }
 
 void Engine::upload_P_full(const std::vector<double> &Ph, int N) {
@@ -1109,8 +1107,8 @@ int Engine::aux_walk_standalone(double *P, int N, int ld, int ntab, const int *i
   });
 }
 
-// One position fix through k_fix_rows -> k_fix_M -> k_fix_update (Engine::fix_update_chain's launches for a chain of
-// one) on a caller's covariance at a caller's pose
+// One position fix through k_fix_rows -> k_chain_M -> k_chain_update (Engine::fix_update_chain's launches for a chain
+// of one) on a caller's covariance at a caller's pose
 int Engine::position_update_standalone(double *P, int N, int ld, int imu_id, const double *q, const double *p,
                                        int aux_id, const double *s, int r, const double *C, const double *z,
                                        const double *R, int ldr, double chi2_thr, double *dx, double *chi2,
@@ -1136,27 +1134,30 @@ int Engine::position_update_standalone(double *P, int N, int ld, int imu_id, con
   st.id_imu = imu_id;
   st.nf = 1;
   DevBuf<DFixState> dst;
-  DevBuf<DFixRow> drow;
-  DevBuf<double> dM, dreg;
-  std::vector<double> reg((size_t)N + 4, 0.0);
+  DevBuf<DChainRow> drow;
+  DevBuf<double> dM;
+  DevBuf<unsigned char> dreg;
+  std::vector<double> reg((size_t)N + kChainHeader, 0.0);
   const int rc = aux_standalone_run(P, (size_t)N, ld, [&](hipStream_t sm, double *dP) {
     dst = DevBuf<DFixState>(1);
-    drow = DevBuf<DFixRow>(1);
+    drow = DevBuf<DChainRow>(1);
     dM = DevBuf<double>((size_t)3 * N);
-    dreg = DevBuf<double>(reg.size());
+    dreg = DevBuf<unsigned char>(sizeof(double) * reg.size());
+    DChainRegion *region = chain_region(dreg, reg.size(), 0);
     HP_HIP(hipMemcpyAsync(dst, &st, sizeof(st), hipMemcpyHostToDevice, sm));
     HP_HIP(hipMemsetAsync(dreg, 0, sizeof(double) * reg.size(), sm));
-    launch_fix_rows(sm, dst, 0, nullptr, drow, dreg);
-    launch_fix_M(sm, dP, ld, N, drow, r, dM);
-    launch_fix_update(sm, dP, ld, N, dM, drow, r, dreg);
+    launch_fix_rows(sm, dst, 0, nullptr, drow, region);
+    launch_chain_M(sm, dP, ld, N, drow, r, dM);
+    launch_chain_update(sm, dP, ld, N, dM, drow, r, false, region);
     HP_HIP(hipMemcpyAsync(reg.data(), dreg, sizeof(double) * reg.size(), hipMemcpyDeviceToHost, sm));
   });
   if (rc) return rc;
-  *chi2 = reg[2];
-  *applied = reg[0] != 0.0 ? 1 : 0;
-  for (int i = 0; i < N; i++) dx[i] = *applied ? reg[(size_t)4 + i] : 0.0;
-  if (reg[3] != 0.0) return UVIO_HP_E_ARG;  // S is not positive definite: nothing was applied
-  if (*applied && *reinterpret_cast<const int *>(&reg[1]) > 0) return UVIO_HP_E_NUMERIC;
+  const DChainRegion g = chain_header(reg.data());
+  *chi2 = g.chi2;
+  *applied = g.accepted != 0.0 ? 1 : 0;
+  for (int i = 0; i < N; i++) dx[i] = *applied ? reg[kChainHeader + i] : 0.0;
+  if (g.extra != 0.0) return UVIO_HP_E_ARG;  // refused: S is not positive definite, nothing was applied
+  if (*applied && g.neg > 0) return UVIO_HP_E_NUMERIC;
   return 0;
 }
 

@@ -1331,10 +1331,22 @@ int Engine::uwb_update_single(size_t anchor_id, double range) {
   return uwb_update_message({{anchor_id, range}});
 }
 
+template <class F>
+const double *Engine::run_mchain(int n, F &&enqueue) {
+  for (int j = 0; j < n; j++)
+    enqueue(j, j ? chain_region(d_.mchain_reg, d_.mchain_stride, j - 1) : nullptr, d_.mchain_row + j,
+            chain_region(d_.mchain_reg, d_.mchain_stride, j));
+  ++p_epoch_;
+  const size_t len = (size_t)(n - 1) * d_.mchain_stride + kChainHeader + N_;
+  HP_HIP(hipMemcpyAsync(d_.mchain_host, d_.mchain_reg, sizeof(double) * len, hipMemcpyDeviceToHost, d_.stream));
+  dev_sync();
+  return d_.mchain_host;
+}
+
 // The ranges of one message as ONE device chain (UVioManager.cpp:178-188 runs update_single per range, each
 // linearized at the state the previous one left): the linearization state (IMU pose, p_IinU, the message's
 // anchors) goes up once; per range k_uwb_row moves it by the previous range's dx when that was accepted (Var::update's
-// formulas) and forms the row, k_uwb_M forms M = P[:, I] h, k_uwb_update gates chi2 = res^2 / S on the device and
+// formulas) and forms the row, k_chain_M forms M = P[:, I] h, k_chain_update gates chi2 = res^2 / S on the device and
 // updates P and dx when accepted.  One readback returns every range's [accepted, negative diagonals, chi2, S | dx];
 // the host then applies the accepted dx's to its mean in order (the same values the device state moved by), so
 // each row is linearized exactly where the per-range path linearized it -- with two host waits per range (S for
@@ -1348,55 +1360,40 @@ int Engine::uwb_update_message(const std::vector<std::pair<size_t, double>> &ran
     std::memcpy(st.q, imu_->val, sizeof(double) * 4);
     std::memcpy(st.p, imu_->val + 4, sizeof(double) * 3);
     std::memcpy(st.pU, p_IinU_->val, sizeof(double) * 3);
+    st.s2 = o_.uwb_sigma_range * o_.uwb_sigma_range;
+    st.thr = o_.uwb_chi2_multipler * chi2_table_[1];
     st.id_imu = imu_->id;
     st.id_cal = o_.do_calib_uwb_extrinsics ? p_IinU_->id : -1;
     st.nr = nr;
-    std::vector<int> hidx;
-    std::vector<int> off(nr), ncol(nr);
     for (int j = 0; j < nr; j++) {
       const VarP &an = anchors_.at(ranges[c0 + j].first);
       std::memcpy(st.anc[j], an->val, sizeof(double) * 5);
       st.range[j] = ranges[c0 + j].second;
       st.id_anc[j] = an->fixed ? -1 : an->id;
-      off[j] = (int)hidx.size();
-      for (int k = 0; k < 6; k++) hidx.push_back(imu_->id + k);
-      if (o_.do_calib_uwb_extrinsics)
-        for (int k = 0; k < 3; k++) hidx.push_back(p_IinU_->id + k);
-      if (!an->fixed)
-        for (int k = 0; k < 5; k++) hidx.push_back(an->id + k);
-      ncol[j] = (int)hidx.size() - off[j];
     }
     DUwbState *dst = stage(&st, 1);
-    const int *dh = stage(hidx.data(), hidx.size());
     stage_flush();
-    const double s2 = o_.uwb_sigma_range * o_.uwb_sigma_range;
-    const double thr = o_.uwb_chi2_multipler * chi2_table_[1];
+    const double *host = run_mchain(nr, [&](int j, const DChainRegion *prev, DChainRow *row, DChainRegion *reg) {
+      launch_uwb_row(d_.stream, dst, j, prev, row, reg);
+      launch_chain_M(d_.stream, d_.P, d_.ldp, N_, row, 1, d_.ekf.M);
+      launch_chain_update(d_.stream, d_.P, d_.ldp, N_, d_.ekf.M, row, 1, true, reg);
+    });
     for (int j = 0; j < nr; j++) {
-      double *reg = d_.uwb_reg + (size_t)j * d_.uwb_stride, *h = d_.uwb_h + 16 * j;
-      launch_uwb_row(d_.stream, dst, j, j ? reg - d_.uwb_stride : nullptr, h, reg);
-      launch_uwb_M(d_.stream, d_.P, d_.ldp, N_, h, dh + off[j], ncol[j], d_.ekf.M);
-      launch_uwb_update(d_.stream, d_.P, d_.ldp, N_, d_.ekf.M, h, dh + off[j], ncol[j], s2, thr, reg);
-    }
-    ++p_epoch_;
-    const size_t n = (size_t)(nr - 1) * d_.uwb_stride + 4 + N_;
-    HP_HIP(hipMemcpyAsync(d_.uwb_host, d_.uwb_reg, sizeof(double) * n, hipMemcpyDeviceToHost, d_.stream));
-    dev_sync();
-    for (int j = 0; j < nr; j++) {
-      const double *reg = d_.uwb_host + (size_t)j * d_.uwb_stride;
-      if (reg[0] == 0.0) continue;
-      if (*reinterpret_cast<const int *>(reg + 1) > 0)
-        throw HpError(UVIO_HP_E_NUMERIC, "UWB EKFUpdate: negative covariance diagonal");
-      apply_dx(reg + 4);
+      const double *reg = host + (size_t)j * d_.mchain_stride;
+      const DChainRegion g = chain_header(reg);
+      if (g.accepted == 0.0) continue;
+      if (g.neg > 0) throw HpError(UVIO_HP_E_NUMERIC, "UWB EKFUpdate: negative covariance diagonal");
+      apply_dx(reg + kChainHeader);
       applied++;
     }
   }
   return applied;
 }
 
-// The position fixes of one timestamp as device chains shaped like uwb_update_message's: the linearization state
+// The position fixes of one timestamp as device chains like uwb_update_message's: the linearization state
 // (IMU pose, every fix's lever arm) goes up once per chain; per fix k_fix_rows moves it by the previous fix's dx when
-// that was accepted and forms H and the residual, k_fix_M forms M = P[:, I] H^T, k_fix_update factors S, gates chi2 on
-// the device and updates P and dx when accepted.  One readback returns every fix's
+// that was accepted and forms H and the residual, k_chain_M forms M = P[:, I] H^T, k_chain_update factors S, gates
+// chi2 on the device and updates P and dx when accepted.  One readback returns every fix's
 // [accepted, negative diagonals, chi2, refused | dx]; the host then applies the accepted dx's to its mean in order.
 // An aux lever arm is looked up here, at replay: its covariance offset moves when clones in front of it are
 // marginalized, and a handle removed since the feed refuses its fix (status 3) without touching the state.
@@ -1433,29 +1430,23 @@ void Engine::fix_update_chain(double t, const std::vector<FixMeas> &fixes) {
     }
     DFixState *dst = stage(&st, 1);
     stage_flush();
-    for (int j = 0; j < nf; j++) {
-      double *reg = d_.uwb_reg + (size_t)j * d_.uwb_stride;
-      const DFixRow *row = d_.fix_row + j;
-      launch_fix_rows(d_.stream, dst, j, j ? reg - d_.uwb_stride : nullptr, d_.fix_row + j, reg);
-      launch_fix_M(d_.stream, d_.P, d_.ldp, N_, row, st.r[j], d_.ekf.M);
-      launch_fix_update(d_.stream, d_.P, d_.ldp, N_, d_.ekf.M, row, st.r[j], reg);
-    }
-    ++p_epoch_;
-    const size_t n = (size_t)(nf - 1) * d_.uwb_stride + 4 + N_;
-    HP_HIP(hipMemcpyAsync(d_.uwb_host, d_.uwb_reg, sizeof(double) * n, hipMemcpyDeviceToHost, d_.stream));
-    dev_sync();
+    const double *host = run_mchain(nf, [&](int j, const DChainRegion *prev, DChainRow *row, DChainRegion *reg) {
+      launch_fix_rows(d_.stream, dst, j, prev, row, reg);
+      launch_chain_M(d_.stream, d_.P, d_.ldp, N_, row, st.r[j], d_.ekf.M);
+      launch_chain_update(d_.stream, d_.P, d_.ldp, N_, d_.ekf.M, row, st.r[j], false, reg);
+    });
     bool applied = false;
     for (int j = 0; j < nf; j++) {
-      const double *reg = d_.uwb_host + (size_t)j * d_.uwb_stride;
+      const double *reg = host + (size_t)j * d_.mchain_stride;
+      const DChainRegion g = chain_header(reg);
       FixResult &res = fix_results_[slot[c0 + j]];
-      res.chi2 = reg[2];
-      if (reg[0] == 0.0) {
-        res.status = reg[3] != 0.0 ? 3 : 1;
+      res.chi2 = g.chi2;
+      if (g.accepted == 0.0) {
+        res.status = g.extra != 0.0 ? 3 : 1;
         continue;
       }
-      if (*reinterpret_cast<const int *>(reg + 1) > 0)
-        throw HpError(UVIO_HP_E_NUMERIC, "position fix EKFUpdate: negative covariance diagonal");
-      apply_dx(reg + 4);
+      if (g.neg > 0) throw HpError(UVIO_HP_E_NUMERIC, "position fix EKFUpdate: negative covariance diagonal");
+      apply_dx(reg + kChainHeader);
       res.status = 0;
       applied = true;
     }

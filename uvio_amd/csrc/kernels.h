@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -209,6 +210,55 @@ void launch_gram_reduce_chol(hipStream_t s, const double *partials, int nchunks,
 constexpr int kMaxEkfRows = 255;        // rows of one direct (uncompressed) EKF update (+ residual <= 256)
 constexpr int kMaxDynLds = 152 * 1024;  // dynamic LDS budget of the single-workgroup solvers
 // S holds 5 r^2 doubles for r rows
+// Device chains of small measurements (UWB ranges: Engine::uwb_update_message; position fixes:
+// Engine::fix_update_chain): per step three launches, a row kernel (k_uwb_row / k_fix_rows) that moves the chain's
+// linearization state by the previous step's dx when that was accepted and leaves one DChainRow, then k_chain_M and
+// k_chain_update, which are the same for both.  Step j owns one region of the chain's buffer: this header, then dx
+// (N doubles).  The host reads every region back in one copy.
+struct DChainRegion {
+  double accepted;  // 1.0: P and dx were updated
+  int neg;          // negative covariance diagonals the update left (StateHelper.cpp:181)
+  int halt;         // an earlier step of the chain left a negative diagonal: this step did not run
+  double chi2;
+  double extra;     // a range: S; a fix: refused (S not positive definite, or a NaN chi2)
+  double dx[];      // N doubles
+};
+static_assert(sizeof(DChainRegion) == 32 && sizeof(DChainRegion) % alignof(double) == 0, "four doubles, then dx");
+static_assert(offsetof(DChainRegion, accepted) == 0 && offsetof(DChainRegion, neg) == 8 &&
+                  offsetof(DChainRegion, halt) == 12 && offsetof(DChainRegion, chi2) == 16 &&
+                  offsetof(DChainRegion, extra) == 24 && offsetof(DChainRegion, dx) == 32,
+              "the readback layout [accepted, neg | halt, chi2, extra | dx]");
+constexpr size_t kChainHeader = sizeof(DChainRegion) / sizeof(double);  // dx starts this many doubles in
+// step j's region in a chain buffer of stride doubles per step (raw device bytes, typed here and nowhere else)
+inline DChainRegion *chain_region(unsigned char *buf, size_t stride, int j) {
+  return static_cast<DChainRegion *>(static_cast<void *>(buf + (size_t)j * stride * sizeof(double)));
+}
+// the header of a region in the host's readback (doubles)
+inline DChainRegion chain_header(const double *region) {
+  DChainRegion g;
+  std::memcpy(&g, region, sizeof(g));
+  return g;
+}
+// what a row kernel leaves for k_chain_M and k_chain_update: r rows over n columns
+constexpr int kChainMaxCols = 14;  // a UWB row: 6 IMU columns, 3 for p_IinU, 5 for the anchor; a fix: 6 or 9
+struct DChainRow {
+  double H[3][kChainMaxCols];  // r x n
+  double res[3];
+  double R[9];                 // leading dimension 3 (a range: R[0] = sigma^2)
+  double thr;                  // chi2 threshold
+  int hidx[kChainMaxCols];     // covariance index of H's column k
+  int n, pad;
+};
+// M = P[:, hidx] H^T as r column arrays of length N (column c at M + c N), fma in ascending k
+void launch_chain_M(hipStream_t s, const double *P, int ldp, int N, const DChainRow *row, int r, double *M);
+// S = H M[hidx, :] + R and the step's gate, the same arithmetic in every workgroup; accepted: P -= W W^T and dx.
+//   range (r = 1): chi2 = res^2 / S against row->thr (a NaN chi2 passes, as in UpdaterUWB.cpp:73-79), W = M / sqrt S,
+//                  dx = W res / sqrt S, extra = S
+//   fix (r = 1 .. 3): S = L L^T in registers (a pivot that is not finite or not positive, or a NaN chi2: refused),
+//                  chi2 = |L^-1 res|^2 against row->thr, W = M L^-T, dx = W L^-1 res, extra = refused
+void launch_chain_update(hipStream_t s, double *P, int ldp, int N, const double *M, const DChainRow *row, int r,
+                         bool range, DChainRegion *region);
+
 // The ranges of one UwbData message as one device chain (Engine::uwb_update_message; UpdaterUWB::update_single,
 // UpdaterUWB.cpp:53-90, per range in the message's order): the linearization state of the message's rows, moved
 // by each accepted range's dx on the device with Var::update's formulas
@@ -218,22 +268,19 @@ struct DUwbState {
   double pU[3];                    // p_IinU
   double anc[kUwbMaxRanges][5];    // range j's anchor [p_AinG, const_bias, dist_bias]
   double range[kUwbMaxRanges];
+  double s2, thr;                  // the range noise sigma^2 and the chi2 threshold of every row
   int id_imu, id_cal;              // covariance ids (id_cal < 0: p_IinU not calibrated)
   int id_anc[kUwbMaxRanges];       // < 0: fixed anchor (no columns)
   int nr;
 };
 // range j: apply range j-1's dx to the state if it was accepted (prev: its region, null for j = 0), then form
-// the row h (n + 1 doubles, residual last) and zero the region's header
-void launch_uwb_row(hipStream_t s, DUwbState *st, int j, const double *prev, double *h, double *region);
-// M = P[:, hidx] h
-void launch_uwb_M(hipStream_t s, const double *P, int ldp, int N, const double *h, const int *hidx, int n, double *M);
-// S = h^T M[hidx] + s2, chi2 = res^2 / S against thr; accepted: P -= W W^T (W = M / sqrt S), dx = W res / sqrt S.
-// region: [accepted, negative diagonals (int), chi2, S | dx (N)]
-void launch_uwb_update(hipStream_t s, double *P, int ldp, int N, const double *M, const double *h, const int *hidx,
-                       int n, double s2, double thr, double *region);
+// the row (uwb_row's h over the columns [IMU (6), p_IinU (3) if calibrated, anchor (5) if free]) and reset the
+// region's header; a negative diagonal or a halt in prev halts this range too
+void launch_uwb_row(hipStream_t s, DUwbState *st, int j, const DChainRegion *prev, DChainRow *row,
+                    DChainRegion *region);
 
 // Buffered position fixes (include/uvio_hp.h uvio_hp_feed_position; Engine::fix_update_chain): the fixes that share
-// one timestamp as one device chain shaped like the UWB one.  z = C (p_IinG + R_GtoI^T s) + noise(R), r = 1 .. 3 rows,
+// one timestamp as one device chain.  z = C (p_IinG + R_GtoI^T s) + noise(R), r = 1 .. 3 rows,
 // s a constant lever arm or a live 3-dimensional aux variable; H over the error state is
 // C [-R_GtoI^T [s]x | I | R_GtoI^T], the last block only for an aux lever arm (JPL left error).
 constexpr int kFixMaxChain = 8;    // fixes of one chain (one readback); more at one timestamp run as several chains
@@ -249,26 +296,12 @@ struct DFixState {
   int id_aux[kFixMaxChain];       // covariance id of the aux lever arm, < 0: constant
   int id_imu, nf;
 };
-// what k_fix_rows leaves for the other two kernels of fix j
-struct DFixRow {
-  double H[3][9];   // r x n, n = 6 or 9
-  double res[3];    // z - C pred
-  double R[9];      // leading dimension 3
-  double thr;
-  int hidx[9];      // covariance index of H's column k
-  int n, pad;
-};
 // fix j: move the linearization state by fix j-1's dx if that was accepted (prev: its region, null for j = 0), form
-// the row block and zero the region's header [accepted, negative diagonals (int) | halt (int), chi2, refused];
-// a negative diagonal or a halt in prev halts this fix too
-void launch_fix_rows(hipStream_t s, DFixState *st, int j, const double *prev, DFixRow *row, double *region);
-// M = P[:, hidx] H^T as r column arrays of length N (column c at M + c N)
-void launch_fix_M(hipStream_t s, const double *P, int ldp, int N, const DFixRow *row, int r, double *M);
-// S = H M[hidx, :] + R = L L^T in registers (a pivot that is not finite or not positive, or a NaN chi2: refused),
-// chi2 = |L^-1 res|^2 against row->thr; accepted: P -= W W^T (W = M L^-T), dx = W L^-1 res.
-// region: [accepted, negative diagonals (int) | halt (int), chi2, refused | dx (N)]
-void launch_fix_update(hipStream_t s, double *P, int ldp, int N, const double *M, const DFixRow *row, int r,
-                       double *region);
+// the row block (n = 6, or 9 with an aux lever arm) and reset the region's header; a negative diagonal or a halt in
+// prev halts this fix too
+void launch_fix_rows(hipStream_t s, DFixState *st, int j, const DChainRegion *prev, DChainRow *row,
+                     DChainRegion *region);
+constexpr int kChainMaxSteps = kUwbMaxRanges > kFixMaxChain ? kUwbMaxRanges : kFixMaxChain;
 
 struct EkfScratch {
   double *M, *W, *S, *y, *dx;
@@ -313,7 +346,7 @@ void launch_ekf_phaseB(hipStream_t s, double *P, int ldp, int N, int r, const do
                        EkfScratch &sc);
 // The same update with a caller's dense noise matrix R (r x r, ld ldr, device; only its upper triangle is read, as
 // S.triangularView<Upper>() += R, StateHelper.cpp:156) behind a chi2 gate on the update's own factor
-// (UpdaterUWB.cpp:67-79): phase A with sigma2 = 0, then k_ekf_fact_R, then k_ekf_WP behind the gate.
+// (UpdaterUWB.cpp:67-79): phase A with sigma2 = 0, then k_ekf_fact's dense-R instance, then k_ekf_WP behind the gate.
 // sc.chi2_gate (required; its incoming value is not read) receives accepted = every pivot of S finite and > 0,
 // chi2 = res^T S^-1 res finite and not above chi2_thr; [chi2, accepted] go to sc.dx[N], sc.dx[N + 1], chi2 as NaN
 // when a pivot is bad.  Not accepted: P and sc.dx[0 .. N) are left as they were.  sc.Tall must be null.

@@ -462,12 +462,8 @@ __global__ void __launch_bounds__(256) k_gram(const double *__restrict__ A, int 
   // tile pair (ti <= tj)
   const int npairs = nt * (nt + 1) / 2, wid = xcd_swizzle(blockIdx.x, gridDim.x);
   const int chunk = wid / npairs;
-  int pair = wid - chunk * npairs, ti = 0;
-  while (pair >= nt - ti) {
-    pair -= nt - ti;
-    ti++;
-  }
-  int tj = ti + pair;
+  int ti, tj;
+  upper_pair(wid - chunk * npairs, nt, ti, tj);
   int r0 = chunk * crows, r1 = min(m, r0 + crows);
   int tx = threadIdx.x % 16, ty = threadIdx.x / 16;
   double acc[2][2] = {{0, 0}, {0, 0}};
@@ -516,12 +512,8 @@ __global__ void __launch_bounds__(256) k_gram_mfma(const double *__restrict__ A,
   const int nt = (ncol + GB - 1) / GB, npairs = nt * (nt + 1) / 2;
   // work index = chunk * npairs + pair, XCD-swizzled: a chunk's tile pairs share one XCD's L2
   const int wid = xcd_swizzle(blockIdx.x, gridDim.x), chunk = wid / npairs;
-  int pair = wid - chunk * npairs, ti = 0;
-  while (pair >= nt - ti) {
-    pair -= nt - ti;
-    ti++;
-  }
-  const int tj = ti + pair;
+  int ti, tj;
+  upper_pair(wid - chunk * npairs, nt, ti, tj);
   const int c0i = ti * GB, c0j = tj * GB;
   const int r0 = chunk * GCHUNK_BIG, r1 = min(m, r0 + GCHUNK_BIG);
   constexpr int NU = GK / 4;  // slab elements per thread
@@ -1240,12 +1232,8 @@ __global__ void __launch_bounds__(256) k_info_P(double *__restrict__ P, int ldp,
   __shared__ double red[2][4][256];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int r16 = lane & 15, kq = lane >> 4;
-  int bi = 0;
-  while (b >= nb - bi) {
-    b -= nb - bi;
-    bi++;
-  }
-  const int bj = bi + b;
+  int bi, bj;
+  upper_pair(b, nb, bi, bj);
   // this thread's P element, fetched before the products so its latency is hidden
   const int ei = threadIdx.x >> 4, ej = threadIdx.x & 15;
   const int gi = 16 * bi + ei, gj = 16 * bj + ej;

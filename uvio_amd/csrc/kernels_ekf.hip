@@ -6,7 +6,8 @@
 //                     T = H P_II read from the batch's chi2 gate in the same launch, or gathered from the rows
 //                     I of this update's own M in a second launch
 //   k_ekf_fact one workgroup: LDL^T of [S ; r^T] in LDS with the unit-lower inverse alongside (dense_lds.h
-//                     ldl_wave) -> L^-1, y = L^-1 r, and StateHelper::initialize's chi2 gate on y
+//                     ldl_wave) -> L^-1, y = L^-1 r, and StateHelper::initialize's chi2 gate on y; its DENSE_R
+//                     instances add a caller's dense R to S and gate on the pivots too (launch_ekf_update_R)
 //   k_ekf_WP   grid over the upper 16x16 tile pairs (bi <= bj) of P: W_b = M_b L^-T for both row blocks
 //                     (a GEMM with the explicit inverse, recomputed per tile pair instead of a separate
 //                     launch), P_ij -= W_bi W_bj^T (written to both triangles), dx = W y on diagonal tiles
@@ -15,6 +16,10 @@
 // and dx = (M L^-T)(L^-1 r): the same update (S = L L^T), every product on MFMA tiles.  The earlier chain
 // (k_ekf_M, k_ekf_S, k_ekf_small, k_trinv16, k_trsm_lt, k_ekf_P: six launches, VALU tiles for the four
 // products) cost 96 us per update at cfg2 in rocprof (profiles/r01g_cfg2_per_frame.txt).
+//
+// Also here: the delayed-initialization candidate (k_di_M, k_di_S, k_chain_apply) and the device chains of small
+// measurements, UWB ranges and position fixes: a row kernel (k_uwb_row / k_fix_rows), then k_chain_M and
+// k_chain_update<RangeGate | FixGate<R>> for both.
 //
 // MFMA operand layout (f64 16x16x4): A (16x4) lane l holds A[l & 15][l >> 4]; B (4x16) lane l holds
 // B[l >> 4][l & 15]; C/D register q of lane l is D[(l >> 4) + 4 q][l & 15].
@@ -90,13 +95,10 @@ __global__ void __launch_bounds__(kMSThreads) k_ekf_MS(const double *__restrict_
     __syncthreads();
   }
   const int nt = (r + 15) / 16;
-  int pair = (blockIdx.x - nbM) * (kMSThreads / 64) + wid, at = 0;
+  const int pair = (blockIdx.x - nbM) * (kMSThreads / 64) + wid;
   if (pair >= nt * (nt + 1) / 2) return;
-  while (pair >= nt - at) {
-    pair -= nt - at;
-    at++;
-  }
-  const int bt = at + pair;
+  int at, bt;
+  upper_pair(pair, nt, at, bt);
   const int ar = 16 * at + r16, br = 16 * bt + r16;
   const double *Ha = H + (size_t)min(ar, r - 1) * ldh;
   const double *Tb = gath ? Tall + min(br, r - 1) : Tall + (size_t)min(br, r - 1) * ldt;
@@ -129,15 +131,25 @@ static size_t ekf_ms_lds_bytes(int n) { return (size_t)16 * (n | 1) * sizeof(dou
 // LDS: the factor in LDS (a compile-time choice, so every access of the factorization is a DS instruction;
 // a runtime choice makes them all FLAT)
 // W: the panel waves of ldl_wave_inv (panel rows 16 + 48 W); one workgroup of kFactThreads.
-template <int W, bool LDS>
+// DENSE_R: a caller's dense noise matrix (launch_ekf_update_R): S = S_up + R, where S_up = H P_II H^T comes from
+// k_ekf_MS with s2 = 0 and only R's upper triangle (r x r, ld ldr, device) is read, as the reference's
+// S.triangularView<Upper>() += R (StateHelper.cpp:156).  With R = s2 I the staged values are k_ekf_MS's own
+// (acc + 0.0) + s2, so the factor, L^-1 and y are the plain instance's bit for bit.
+// The two gates differ, and are kept apart on purpose:
+//   plain  optional (chi2_gate may be null); accepted = incoming *chi2_gate (the feature's linearization
+//          succeeded) && !(chi2 > thr), so a NaN chi2 passes
+//   dense  mandatory, the incoming value is not read; a caller's R can make S indefinite, so every pivot Dd[k] has
+//          to be finite and > 0 and chi2 finite: accepted = pivots_ok && isfinite(chi2) && !(chi2 > thr), chi2
+//          written as NaN when a pivot is bad
+// Both: accepted -> *chi2_gate (k_ekf_WP's gate), [chi2, accepted] -> gate_out[0..1].
+template <int W, bool LDS, bool DENSE_R>
 __global__ void __launch_bounds__(kFactThreads) k_ekf_fact(const double *__restrict__ Sup, int r,
+                                                  const double *__restrict__ R, int ldr,
                                                   const double *__restrict__ res, int res_stride,
                                                   double *__restrict__ Linv_out, double *__restrict__ y_out, double *Sg,
-                                                  int use_lds, int *chi2_gate, double chi2_thr,
-                                                  double *__restrict__ gate_out) {
+                                                  int *chi2_gate, double chi2_thr, double *__restrict__ gate_out) {
   extern __shared__ double lds[];
   double *A = LDS ? lds : Sg;
-  (void)use_lds;
   const int ld = r | 1;  // odd row stride: conflict-free 64-bit LDS reads down a column
   double *Dd = A + (size_t)(r + 1) * ld, *sd = Dd + r;
   staged_copy(
@@ -145,7 +157,10 @@ __global__ void __launch_bounds__(kFactThreads) k_ekf_fact(const double *__restr
       [&](int e) {
         if (e >= r * r) return res[(size_t)(e - r * r) * res_stride];
         const int a = e / r, b = e - a * r;
-        return (b <= a) ? Sup[(size_t)b * r + a] : 0.0;
+        if constexpr (DENSE_R)
+          return (b <= a) ? Sup[(size_t)b * r + a] + R[(size_t)b * ldr + a] : 0.0;
+        else
+          return (b <= a) ? Sup[(size_t)b * r + a] : 0.0;
       },
       [&](int e, double v) {
         if (e >= r * r) {
@@ -163,18 +178,30 @@ __global__ void __launch_bounds__(kFactThreads) k_ekf_fact(const double *__restr
     y_out[k] = A[(size_t)r * ld + k] * q;
   }
   __syncthreads();
-  if (chi2_gate && threadIdx.x < 64) {
+  if ((DENSE_R || chi2_gate) && threadIdx.x < 64) {
+    // chi2 = |y|^2: strided by 64, then the wavefront's halves added down to lane 0
     double s = 0.0;
+    int ok = 1;  // dense: every pivot finite and positive
     for (int k = threadIdx.x; k < r; k += 64) {
       const double v = A[(size_t)r * ld + k] * sd[k];
+      if constexpr (DENSE_R) {
+        const double d = Dd[k];
+        ok &= (isfinite(d) && d > 0.0) ? 1 : 0;
+      }
       s += v * v;
     }
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+    for (int o = 32; o > 0; o >>= 1) {
+      s += __shfl_down(s, o, 64);
+      if constexpr (DENSE_R) ok &= __shfl_down(ok, o, 64);
+    }
     if (threadIdx.x == 0) {
-      // the incoming gate (the feature's linearization succeeded) AND the test
-      const int acc = (*chi2_gate != 0) && !(s > chi2_thr);
+      int acc;
+      if constexpr (DENSE_R)
+        acc = ok && isfinite(s) && !(s > chi2_thr);
+      else
+        acc = (*chi2_gate != 0) && !(s > chi2_thr);
       *chi2_gate = acc;
-      gate_out[0] = s;
+      gate_out[0] = (!DENSE_R || ok) ? s : __builtin_nan("");
       gate_out[1] = acc;
     }
   }
@@ -190,77 +217,6 @@ __global__ void __launch_bounds__(kFactThreads) k_ekf_fact(const double *__restr
 }
 size_t ekf_small_lds_bytes(int r) { return (dense_lds_bytes(r + 1, r) + (size_t)2 * r * sizeof(double)); }
 
-// K2 for a caller's dense noise matrix (launch_ekf_update_R): k_ekf_fact on S = S_up + R, where S_up = H P_II H^T
-// comes from k_ekf_MS with s2 = 0 and only R's upper triangle (r x r, ld ldr, device) is read, as the reference's
-// S.triangularView<Upper>() += R (StateHelper.cpp:156).  With R = s2 I the staged values are k_ekf_MS's own
-// (acc + 0.0) + s2, so the factor, L^-1 and y are those of k_ekf_fact bit for bit.
-// A caller's R can make S indefinite, and a NaN chi2 must not pass the gate as it does in k_ekf_fact: every pivot
-// Dd[k] has to be finite and > 0 and chi2 = |y|^2 (k_ekf_fact's summation order) finite.
-//   accepted = pivots_ok && isfinite(chi2) && !(chi2 > thr)  ->  *gate (k_ekf_WP's gate), [chi2, accepted] -> gate_out
-// with chi2 written as NaN when a pivot is bad.
-template <int W, bool LDS>
-__global__ void __launch_bounds__(kFactThreads) k_ekf_fact_R(const double *__restrict__ Sup, int r,
-                                                    const double *__restrict__ R, int ldr,
-                                                    const double *__restrict__ res, int res_stride,
-                                                    double *__restrict__ Linv_out, double *__restrict__ y_out, double *Sg,
-                                                    int *gate, double chi2_thr, double *__restrict__ gate_out) {
-  extern __shared__ double lds[];
-  double *A = LDS ? lds : Sg;
-  const int ld = r | 1;
-  double *Dd = A + (size_t)(r + 1) * ld, *sd = Dd + r;
-  staged_copy(
-      r * r + r,
-      [&](int e) {
-        if (e >= r * r) return res[(size_t)(e - r * r) * res_stride];
-        const int a = e / r, b = e - a * r;
-        return (b <= a) ? Sup[(size_t)b * r + a] + R[(size_t)b * ldr + a] : 0.0;
-      },
-      [&](int e, double v) {
-        if (e >= r * r) {
-          A[(size_t)r * ld + e - r * r] = v;
-        } else {
-          const int a = e / r, b = e - a * r;
-          if (b <= a) A[(size_t)a * ld + b] = v;
-        }
-      });
-  __syncthreads();
-  ldl_wave_inv<1, SqLayout, W>(A, SqLayout{ld}, r, r + 1, Dd, true);
-  for (int k = threadIdx.x; k < r; k += blockDim.x) {
-    const double q = sqrt(Dd[k]);
-    sd[k] = q;
-    y_out[k] = A[(size_t)r * ld + k] * q;
-  }
-  __syncthreads();
-  if (threadIdx.x < 64) {
-    double s = 0.0;
-    int ok = 1;
-    for (int k = threadIdx.x; k < r; k += 64) {
-      const double d = Dd[k], v = A[(size_t)r * ld + k] * sd[k];
-      ok &= (isfinite(d) && d > 0.0) ? 1 : 0;
-      s += v * v;
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-      s += __shfl_down(s, o, 64);
-      ok &= __shfl_down(ok, o, 64);
-    }
-    if (threadIdx.x == 0) {
-      const int acc = ok && isfinite(s) && !(s > chi2_thr);
-      *gate = acc;
-      gate_out[0] = ok ? s : __builtin_nan("");
-      gate_out[1] = acc;
-    }
-  }
-  for (int e = threadIdx.x; e < r * r; e += blockDim.x) {
-    const int a = e / r, b = e - a * r;
-    double v = 0.0;
-    if (b < a)
-      v = A[(size_t)b * ld + a] / sd[a];
-    else if (b == a)
-      v = 1.0 / sd[a];
-    Linv_out[e] = v;
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------
 // K3: tile pair (bi, bj), bi <= bj, of the nb x nb tile grid of P (blocks enumerated row by row)
 __global__ void __launch_bounds__(256) k_ekf_WP(double *__restrict__ P, int ldp, int N, const double *__restrict__ M,
@@ -270,12 +226,8 @@ __global__ void __launch_bounds__(256) k_ekf_WP(double *__restrict__ P, int ldp,
   extern __shared__ double sh[];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int r16 = lane & 15, kq = lane >> 4;
-  int b = blockIdx.x, bi = 0;
-  while (b >= nb - bi) {
-    b -= nb - bi;
-    bi++;
-  }
-  const int bj = bi + b;
+  int bi, bj;
+  upper_pair(blockIdx.x, nb, bi, bj);
   const int ldw = r | 1;
   double *Wi = sh, *Wj = sh + 16 * ldw, *red = sh + 32 * ldw;
   // this thread's P element, fetched before the products so its latency is hidden
@@ -399,19 +351,34 @@ void launch_chain_apply(hipStream_t s, const DFeatOut *fout, const int *gate, co
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Device chains of small measurements (kernels.h DChainRegion / DChainRow): per step a row kernel, k_chain_M,
+// k_chain_update.
+// The head of a row kernel.  A negative covariance diagonal in an earlier step halts the rest of the chain: the
+// reference stops at that update (StateHelper.cpp:181, std::exit), so no later step may touch P (the host then
+// reports E_NUMERIC).  Returns the previous step's dx when the state has to move by it (accepted and not halted),
+// else null; prev is null for the chain's first step.
+__device__ const double *chain_prev_dx(const DChainRegion *prev, bool &halt) {
+  halt = false;
+  if (!prev) return nullptr;
+  halt = prev->neg > 0 || prev->halt != 0;
+  return (prev->accepted != 0.0 && !halt) ? prev->dx : nullptr;
+}
+__device__ void chain_reset(DChainRegion *region, bool halt) {
+  region->accepted = 0.0;
+  region->neg = 0;
+  region->halt = halt ? 1 : 0;
+  region->chi2 = region->extra = 0.0;
+}
+
 // Chained UWB ranges (kernels.h DUwbState)
-__global__ void k_uwb_row(DUwbState *st, int j, const double *__restrict__ prev, double *__restrict__ h,
-                          double *__restrict__ region) {
+__global__ void k_uwb_row(DUwbState *st, int j, const DChainRegion *__restrict__ prev, DChainRow *__restrict__ row,
+                          DChainRegion *__restrict__ region) {
   if (threadIdx.x != 0) return;
   DUwbState &u = *st;
-  // a negative covariance diagonal in an earlier range of the message halts the rest of it: the reference stops
-  // at that update (StateHelper.cpp:181, std::exit), so no later range may touch P (the host then reports E_NUMERIC)
-  const int *pi = reinterpret_cast<const int *>(prev + 1);
-  const bool halt = prev && (pi[0] > 0 || pi[1] != 0);
-  if (prev && prev[0] != 0.0 && !halt) {
+  bool halt;
+  if (const double *dx = chain_prev_dx(prev, halt)) {
     // Var::update of the previous range's dx (engine_state.cpp): IMU quaternion boxplus + position, p_IinU and
     // the anchors additive
-    const double *dx = prev + 4;
     quat_boxplus(u.q, dx + u.id_imu);
     for (int k = 0; k < 3; k++) u.p[k] += dx[u.id_imu + 3 + k];
     if (u.id_cal >= 0)
@@ -420,94 +387,41 @@ __global__ void k_uwb_row(DUwbState *st, int j, const double *__restrict__ prev,
       if (u.id_anc[a] >= 0)
         for (int k = 0; k < 5; k++) u.anc[a][k] += dx[u.id_anc[a] + k];
   }
-  uwb_row(u.q, u.p, u.pU, u.anc[j], u.id_cal >= 0, u.id_anc[j] >= 0, u.range[j], h);
-  region[0] = 0.0;
-  region[1] = 0.0;  // the negative-diagonal count (int bits, low word) and the halt flag (high word)
-  if (halt) reinterpret_cast<int *>(region + 1)[1] = 1;
-  region[2] = region[3] = 0.0;
-}
-
-void launch_uwb_row(hipStream_t s, DUwbState *st, int j, const double *prev, double *h, double *region) {
-  hipLaunchKernelGGL(k_uwb_row, dim3(1), dim3(64), 0, s, st, j, prev, h, region);
-}
-
-__global__ void __launch_bounds__(256) k_uwb_M(const double *__restrict__ P, int ldp, int N, const double *__restrict__ h,
-                                               const int *__restrict__ hidx, int n, double *__restrict__ M) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  const double *Pr = P + (size_t)i * ldp;
-  double a = 0.0;
-  for (int k = 0; k < n; k++) a = fma(Pr[hidx[k]], h[k], a);
-  M[i] = a;
-}
-
-void launch_uwb_M(hipStream_t s, const double *P, int ldp, int N, const double *h, const int *hidx, int n, double *M) {
-  hipLaunchKernelGGL(k_uwb_M, dim3((N + 255) / 256), dim3(256), 0, s, P, ldp, N, h, hidx, n, M);
-}
-
-// tile pair (bi, bj), bi <= bj, of the 16 x 16 tiles of P, one element per thread
-__global__ void __launch_bounds__(256) k_uwb_update(double *__restrict__ P, int ldp, int N, const double *__restrict__ M,
-                                                    const double *__restrict__ h, const int *__restrict__ hidx, int n,
-                                                    double s2, double thr, double *__restrict__ region, int nb) {
-  if (reinterpret_cast<const int *>(region + 1)[1] != 0) return;  // halted (k_uwb_row): not applied, region[0] = 0
-  // the innovation variance and the gate, the same arithmetic in every block
-  double S = 0.0;
-  for (int k = 0; k < n; k++) S = fma(h[k], M[hidx[k]], S);
-  S += s2;
-  const double res = h[n];
-  const double chi2 = res * res / S;
-  const bool acc = !(chi2 > thr);  // UpdaterUWB.cpp:73-79: rejected when chi2 > multiplier * chi2_0.95(1)
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    region[0] = acc ? 1.0 : 0.0;
-    region[2] = chi2;
-    region[3] = S;
+  const bool cal = u.id_cal >= 0, anc = u.id_anc[j] >= 0;
+  double h[kChainMaxCols + 1];
+  const int n = uwb_row(u.q, u.p, u.pU, u.anc[j], cal, anc, u.range[j], h);
+  DChainRow &o = *row;
+  for (int k = 0; k < n; k++) {
+    o.H[0][k] = h[k];
+    // the columns [IMU (6), p_IinU (3) if calibrated, anchor (5) if free]
+    o.hidx[k] = k < 6 ? u.id_imu + k : (cal && k < 9) ? u.id_cal + k - 6 : u.id_anc[j] + k - (cal ? 9 : 6);
   }
-  if (!acc) return;
-  int b = blockIdx.x, bi = 0;
-  while (b >= nb - bi) {
-    b -= nb - bi;
-    bi++;
-  }
-  const int bj = bi + b;
-  const int ei = threadIdx.x >> 4, ej = threadIdx.x & 15;
-  const int gi = 16 * bi + ei, gj = 16 * bj + ej;
-  const double rs = 1.0 / sqrt(S);
-  if (gi < N && gj < N && (bi < bj || ej >= ei)) {
-    const double v = P[(size_t)gi * ldp + gj] - (M[gi] * rs) * (M[gj] * rs);
-    P[(size_t)gi * ldp + gj] = v;
-    P[(size_t)gj * ldp + gi] = v;
-    if (gi == gj && v < 0.0) atomicAdd(reinterpret_cast<int *>(region + 1), 1);
-  }
-  if (bi == bj && ei == 0 && gj < N) region[4 + gj] = (M[gj] * rs) * (res * rs);
+  o.res[0] = h[n];
+  o.R[0] = u.s2;
+  o.thr = u.thr;
+  o.n = n;
+  o.pad = 0;
+  chain_reset(region, halt);
 }
 
-void launch_uwb_update(hipStream_t s, double *P, int ldp, int N, const double *M, const double *h, const int *hidx,
-                       int n, double s2, double thr, double *region) {
-  const int nb = (N + 15) / 16;
-  hipLaunchKernelGGL(k_uwb_update, dim3(nb * (nb + 1) / 2), dim3(256), 0, s, P, ldp, N, M, h, hidx, n, s2, thr, region,
-                     nb);
+void launch_uwb_row(hipStream_t s, DUwbState *st, int j, const DChainRegion *prev, DChainRow *row,
+                    DChainRegion *region) {
+  hipLaunchKernelGGL(k_uwb_row, dim3(1), dim3(64), 0, s, st, j, prev, row, region);
 }
 
-// ---------------------------------------------------------------------------------------------------
-// Chained position fixes (kernels.h DFixState): the UWB chain's three steps for an r-row measurement, r = 1 .. 3
-__global__ void k_fix_rows(DFixState *st, int j, const double *__restrict__ prev, DFixRow *__restrict__ row,
-                           double *__restrict__ region) {
+// Chained position fixes (kernels.h DFixState)
+__global__ void k_fix_rows(DFixState *st, int j, const DChainRegion *__restrict__ prev, DChainRow *__restrict__ row,
+                           DChainRegion *__restrict__ region) {
   if (threadIdx.x != 0) return;
   DFixState &u = *st;
-  // a negative covariance diagonal in an earlier fix of the chain halts the rest of it, as in k_uwb_row
-  bool halt = false;
-  if (prev) {
-    const int *pi = reinterpret_cast<const int *>(prev + 1);
-    halt = pi[0] > 0 || pi[1] != 0;
-    if (prev[0] != 0.0 && !halt) {
-      // Var::update of the previous fix's dx: IMU quaternion boxplus + position, the aux lever arms additive
-      const double *dx = prev + 4;
-      quat_boxplus(u.q, dx + u.id_imu);
-      for (int k = 0; k < 3; k++) u.p[k] += dx[u.id_imu + 3 + k];
-      for (int a = 0; a < u.nf; a++)
-        if (u.id_aux[a] >= 0)
-          for (int k = 0; k < 3; k++) u.s[a][k] += dx[u.id_aux[a] + k];
-    }
+  bool halt;
+  if (const double *dx = chain_prev_dx(prev, halt)) {
+    // Var::update of the previous fix's dx: IMU quaternion boxplus + position, the aux lever arms additive
+    quat_boxplus(u.q, dx + u.id_imu);
+    for (int k = 0; k < 3; k++) u.p[k] += dx[u.id_imu + 3 + k];
+    for (int a = 0; a < u.nf; a++)
+      if (u.id_aux[a] >= 0)
+        for (int k = 0; k < 3; k++) u.s[a][k] += dx[u.id_aux[a] + k];
   }
   const int r = u.r[j];
   const bool aux = u.id_aux[j] >= 0;
@@ -518,7 +432,7 @@ __global__ void k_fix_rows(DFixState *st, int j, const double *__restrict__ prev
   for (int k = 0; k < 3; k++) pred[k] += u.p[k];
   skew(s, Sx);
   m3_mul_at(Rm, Sx, A);  // R_GtoI^T [s]x
-  DFixRow &o = *row;
+  DChainRow &o = *row;
   for (int a = 0; a < 3; a++) {
     for (int k = 0; k < 9; k++) o.H[a][k] = 0.0;
     o.res[a] = 0.0;
@@ -538,19 +452,17 @@ __global__ void k_fix_rows(DFixState *st, int j, const double *__restrict__ prev
   o.thr = u.thr[j];
   o.n = aux ? 9 : 6;
   o.pad = 0;
-  region[0] = 0.0;
-  region[1] = 0.0;  // the negative-diagonal count (int bits, low word) and the halt flag (high word)
-  if (halt) reinterpret_cast<int *>(region + 1)[1] = 1;
-  region[2] = region[3] = 0.0;
+  chain_reset(region, halt);
 }
 
-void launch_fix_rows(hipStream_t s, DFixState *st, int j, const double *prev, DFixRow *row, double *region) {
+void launch_fix_rows(hipStream_t s, DFixState *st, int j, const DChainRegion *prev, DChainRow *row,
+                     DChainRegion *region) {
   hipLaunchKernelGGL(k_fix_rows, dim3(1), dim3(64), 0, s, st, j, prev, row, region);
 }
 
 template <int R>
-__global__ void __launch_bounds__(256) k_fix_M(const double *__restrict__ P, int ldp, int N,
-                                               const DFixRow *__restrict__ row, double *__restrict__ M) {
+__global__ void __launch_bounds__(256) k_chain_M(const double *__restrict__ P, int ldp, int N,
+                                                 const DChainRow *__restrict__ row, double *__restrict__ M) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
   const double *Pr = P + (size_t)i * ldp;
@@ -567,21 +479,101 @@ __global__ void __launch_bounds__(256) k_fix_M(const double *__restrict__ P, int
   for (int c = 0; c < R; c++) M[(size_t)c * N + i] = a[c];
 }
 
-void launch_fix_M(hipStream_t s, const double *P, int ldp, int N, const DFixRow *row, int r, double *M) {
-  if (r < 1 || r > 3) throw std::runtime_error("position fix: " + std::to_string(r) + " rows");
-  auto *k = r == 1 ? k_fix_M<1> : r == 2 ? k_fix_M<2> : k_fix_M<3>;
+void launch_chain_M(hipStream_t s, const double *P, int ldp, int N, const DChainRow *row, int r, double *M) {
+  if (r < 1 || r > 3) throw std::runtime_error("measurement chain: " + std::to_string(r) + " rows");
+  auto *k = r == 1 ? k_chain_M<1> : r == 2 ? k_chain_M<2> : k_chain_M<3>;
   hipLaunchKernelGGL(k, dim3((N + 255) / 256), dim3(256), 0, s, P, ldp, N, row, M);
 }
 
-// tile pair (bi, bj), bi <= bj, of the 16 x 16 tiles of P, one element per thread (k_uwb_update's mapping)
-template <int R>
-__global__ void __launch_bounds__(256) k_fix_update(double *__restrict__ P, int ldp, int N, const double *__restrict__ M,
-                                                    const DFixRow *__restrict__ row, double *__restrict__ region,
-                                                    int nb) {
-  if (reinterpret_cast<const int *>(region + 1)[1] != 0) return;  // halted (k_fix_rows): not applied, region[0] = 0
-  // the innovation covariance, its factor and the gate, the same arithmetic in every block
+// The two gate policies of k_chain_update: from S, what the header gets and whether the step is applied; then the
+// weights w of a row m of M with P[i][j] -= ww(w_i, w_j) and dx[j] = dx(w_j).  They are NOT one policy at R = 1:
+// the range gate lets a NaN chi2 (and a negative S) through as the reference does and divides by sqrt(S) once,
+// the fix gate refuses both and substitutes through its Cholesky factor.  Routing a range through the factor, or
+// making its gate refuse NaN, changes results.
+struct RangeGate {  // UpdaterUWB.cpp:73-79: rejected when chi2 > multiplier * chi2_0.95(1)
+  static constexpr int R = 1;
+  double res, rs;
+  __device__ bool gate(const double (&S)[1][1], const DChainRow &row, double &chi2, double &extra) {
+    res = row.res[0];
+    chi2 = res * res / S[0][0];
+    extra = S[0][0];
+    rs = 1.0 / sqrt(S[0][0]);
+    return !(chi2 > row.thr);
+  }
+  __device__ void weights(const double *m, int, double (&w)[1]) const { w[0] = m[0] * rs; }
+  __device__ double ww(const double (&wi)[1], const double (&wj)[1]) const { return wi[0] * wj[0]; }
+  __device__ double dx(const double (&wj)[1]) const { return wj[0] * (res * rs); }
+};
+template <int R_>
+struct FixGate {  // S = L L^T in registers, y = L^-1 res, chi2 = |y|^2
+  static constexpr int R = R_;
+  double L[R][R], y[R];
+  __device__ bool gate(const double (&S)[R][R], const DChainRow &row, double &chi2_out, double &extra) {
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < R; j++) {
+      double d = S[j][j];
+#pragma unroll
+      for (int k = 0; k < j; k++) d -= L[j][k] * L[j][k];
+      if (!(isfinite(d) && d > 0.0)) bad = true;
+      L[j][j] = sqrt(d);
+#pragma unroll
+      for (int i = j + 1; i < R; i++) {
+        double v = S[j][i];
+#pragma unroll
+        for (int k = 0; k < j; k++) v -= L[i][k] * L[j][k];
+        L[i][j] = v / L[j][j];
+      }
+    }
+    double chi2 = 0.0;
+#pragma unroll
+    for (int i = 0; i < R; i++) {
+      double v = row.res[i];
+#pragma unroll
+      for (int k = 0; k < i; k++) v -= L[i][k] * y[k];
+      y[i] = v / L[i][i];
+      chi2 += y[i] * y[i];
+    }
+    const bool refused = bad || chi2 != chi2;
+    chi2_out = bad ? __builtin_nan("") : chi2;
+    extra = refused ? 1.0 : 0.0;
+    return !refused && !(chi2 > row.thr);
+  }
+  // a row of W = M L^-T: L w^T = m^T by forward substitution
+  __device__ void weights(const double *m, int N, double (&w)[R]) const {
+#pragma unroll
+    for (int c = 0; c < R; c++) {
+      double v = m[(size_t)c * N];
+#pragma unroll
+      for (int k = 0; k < c; k++) v -= L[c][k] * w[k];
+      w[c] = v / L[c][c];
+    }
+  }
+  __device__ double ww(const double (&wi)[R], const double (&wj)[R]) const {
+    double s = 0.0;
+#pragma unroll
+    for (int c = 0; c < R; c++) s += wi[c] * wj[c];
+    return s;
+  }
+  __device__ double dx(const double (&wj)[R]) const {
+    double d = 0.0;
+#pragma unroll
+    for (int c = 0; c < R; c++) d += wj[c] * y[c];
+    return d;
+  }
+};
+
+// tile pair (bi, bj), bi <= bj, of the 16 x 16 tiles of P, one element per thread
+template <class G>
+__global__ void __launch_bounds__(256) k_chain_update(double *__restrict__ P, int ldp, int N,
+                                                      const double *__restrict__ M,
+                                                      const DChainRow *__restrict__ row,
+                                                      DChainRegion *__restrict__ region, int nb) {
+  if (region->halt != 0) return;  // halted (the row kernel): not applied, accepted stays 0
+  // the innovation covariance and the gate, the same arithmetic in every block
+  constexpr int R = G::R;
   const int n = row->n;
-  double S[R][R], L[R][R], y[R];
+  double S[R][R];
 #pragma unroll
   for (int a = 0; a < R; a++)
 #pragma unroll
@@ -590,94 +582,60 @@ __global__ void __launch_bounds__(256) k_fix_update(double *__restrict__ P, int 
       for (int k = 0; k < n; k++) acc = fma(row->H[a][k], M[(size_t)b * N + row->hidx[k]], acc);
       S[a][b] = acc + row->R[3 * a + b];
     }
-  bool bad = false;
-#pragma unroll
-  for (int j = 0; j < R; j++) {
-    double d = S[j][j];
-#pragma unroll
-    for (int k = 0; k < j; k++) d -= L[j][k] * L[j][k];
-    if (!(isfinite(d) && d > 0.0)) bad = true;
-    L[j][j] = sqrt(d);
-#pragma unroll
-    for (int i = j + 1; i < R; i++) {
-      double v = S[j][i];
-#pragma unroll
-      for (int k = 0; k < j; k++) v -= L[i][k] * L[j][k];
-      L[i][j] = v / L[j][j];
-    }
-  }
-  double chi2 = 0.0;
-#pragma unroll
-  for (int i = 0; i < R; i++) {
-    double v = row->res[i];
-#pragma unroll
-    for (int k = 0; k < i; k++) v -= L[i][k] * y[k];
-    y[i] = v / L[i][i];
-    chi2 += y[i] * y[i];
-  }
-  const bool refused = bad || chi2 != chi2;
-  const bool acc = !refused && !(chi2 > row->thr);
+  G g;
+  double chi2, extra;
+  const bool acc = g.gate(S, *row, chi2, extra);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    region[0] = acc ? 1.0 : 0.0;
-    region[2] = bad ? __builtin_nan("") : chi2;
-    region[3] = refused ? 1.0 : 0.0;
+    region->accepted = acc ? 1.0 : 0.0;
+    region->chi2 = chi2;
+    region->extra = extra;
   }
   if (!acc) return;
-  int b = blockIdx.x, bi = 0;
-  while (b >= nb - bi) {
-    b -= nb - bi;
-    bi++;
-  }
-  const int bj = bi + b;
+  int bi, bj;
+  upper_pair(blockIdx.x, nb, bi, bj);
   const int ei = threadIdx.x >> 4, ej = threadIdx.x & 15;
   const int gi = 16 * bi + ei, gj = 16 * bj + ej;
   if (gi >= N || gj >= N) return;
-  // rows gi and gj of W = M L^-T: L w^T = m^T by forward substitution
   double wi[R], wj[R];
-#pragma unroll
-  for (int c = 0; c < R; c++) {
-    double vi = M[(size_t)c * N + gi], vj = M[(size_t)c * N + gj];
-#pragma unroll
-    for (int k = 0; k < c; k++) {
-      vi -= L[c][k] * wi[k];
-      vj -= L[c][k] * wj[k];
-    }
-    wi[c] = vi / L[c][c];
-    wj[c] = vj / L[c][c];
-  }
+  g.weights(M + gi, N, wi);
+  g.weights(M + gj, N, wj);
   if (bi < bj || ej >= ei) {
-    double ww = 0.0;
-#pragma unroll
-    for (int c = 0; c < R; c++) ww += wi[c] * wj[c];
-    const double v = P[(size_t)gi * ldp + gj] - ww;
+    const double v = P[(size_t)gi * ldp + gj] - g.ww(wi, wj);
     P[(size_t)gi * ldp + gj] = v;
     P[(size_t)gj * ldp + gi] = v;
-    if (gi == gj && v < 0.0) atomicAdd(reinterpret_cast<int *>(region + 1), 1);
+    if (gi == gj && v < 0.0) atomicAdd(&region->neg, 1);
   }
-  if (bi == bj && ei == 0) {
-    double d = 0.0;
-#pragma unroll
-    for (int c = 0; c < R; c++) d += wj[c] * y[c];
-    region[4 + gj] = d;
-  }
+  if (bi == bj && ei == 0) region->dx[gj] = g.dx(wj);
 }
 
-void launch_fix_update(hipStream_t s, double *P, int ldp, int N, const double *M, const DFixRow *row, int r,
-                       double *region) {
-  if (r < 1 || r > 3) throw std::runtime_error("position fix: " + std::to_string(r) + " rows");
+void launch_chain_update(hipStream_t s, double *P, int ldp, int N, const double *M, const DChainRow *row, int r,
+                         bool range, DChainRegion *region) {
+  if (r < 1 || r > 3 || (range && r != 1))
+    throw std::runtime_error("measurement chain: " + std::to_string(r) + " rows");
   const int nb = (N + 15) / 16;
-  auto *k = r == 1 ? k_fix_update<1> : r == 2 ? k_fix_update<2> : k_fix_update<3>;
+  auto *k = range    ? k_chain_update<RangeGate>
+            : r == 1 ? k_chain_update<FixGate<1>>
+            : r == 2 ? k_chain_update<FixGate<2>>
+                     : k_chain_update<FixGate<3>>;
   hipLaunchKernelGGL(k, dim3(nb * (nb + 1) / 2), dim3(256), 0, s, P, ldp, N, M, row, region, nb);
 }
 
 static void ensure_ekf_lds_attrs() {
   static bool done = false;
   if (done) return;
-  const void *fns[7] = {(const void *)k_ekf_MS,            (const void *)k_ekf_WP,
-                        (const void *)k_ekf_fact<1, true>, (const void *)k_ekf_fact<2, true>,
-                        (const void *)k_ekf_fact<3, true>, (const void *)k_ekf_fact<4, true>,
-                        (const void *)k_ekf_fact<5, true>};
-  for (int k = 0; k < 7; k++)
+  const void *fns[12] = {(const void *)k_ekf_MS,
+                         (const void *)k_ekf_WP,
+                         (const void *)k_ekf_fact<1, true, false>,
+                         (const void *)k_ekf_fact<2, true, false>,
+                         (const void *)k_ekf_fact<3, true, false>,
+                         (const void *)k_ekf_fact<4, true, false>,
+                         (const void *)k_ekf_fact<5, true, false>,
+                         (const void *)k_ekf_fact<1, true, true>,
+                         (const void *)k_ekf_fact<2, true, true>,
+                         (const void *)k_ekf_fact<3, true, true>,
+                         (const void *)k_ekf_fact<4, true, true>,
+                         (const void *)k_ekf_fact<5, true, true>};
+  for (int k = 0; k < 12; k++)
     if (set_dyn_lds(fns[k], kMaxDynLds) < kMaxDynLds)
       throw std::runtime_error("dynamic LDS limit not granted for an EKF kernel (" + std::to_string(k) + ")");
   done = true;
@@ -704,37 +662,52 @@ void launch_ekf_phaseA(hipStream_t s, const double *P, int ldp, int N, const dou
                      nbM, sc.neg, sc.Tall, sc.ldt, sc.kmask_tile);
 }
 
-static void launch_ekf_factor(hipStream_t s, int N, int r, const double *res, int res_stride, EkfScratch &sc) {
+template <bool LDS, bool DENSE_R>
+static auto ekf_fact_instance(int w) {
+  return w == 1   ? k_ekf_fact<1, LDS, DENSE_R>
+         : w == 2 ? k_ekf_fact<2, LDS, DENSE_R>
+         : w == 3 ? k_ekf_fact<3, LDS, DENSE_R>
+         : w == 4 ? k_ekf_fact<4, LDS, DENSE_R>
+                  : k_ekf_fact<5, LDS, DENSE_R>;
+}
+
+// k_ekf_fact on sc.S's S_up (+ R when R is given: the dense gate against chi2_thr into sc.chi2_gate, else the
+// plain gate of sc.chi2_gate / sc.chi2_thr when the scratch has one)
+static void launch_ekf_factor(hipStream_t s, int N, int r, const double *res, int res_stride, EkfScratch &sc,
+                              const double *R = nullptr, int ldr = 0, double chi2_thr = 0.0) {
   ensure_ekf_lds_attrs();
   if (r + 1 > kWaveMaxRows) throw std::runtime_error("direct EKF update with more rows than the factorization panel");
   const size_t bytes = ekf_small_lds_bytes(r);
-  const int use_lds = bytes <= (size_t)kMaxDynLds;
+  const bool use_lds = bytes <= (size_t)kMaxDynLds;
   double *Linv = sc.S;
   double *Sup = sc.S + 2 * (size_t)r * r;
   double *Sg = sc.S + 3 * (size_t)r * r;  // (r+1)(r|1) + 2r <= 2 r^2 doubles once r >= 40 (else LDS)
   {
     KScope ks(sc.kp, KC_LDL);
     const int w = panel_waves(r + 1);
-    auto *kf = use_lds ? (w == 1 ? k_ekf_fact<1, true> : w == 2 ? k_ekf_fact<2, true> : w == 3 ? k_ekf_fact<3, true>
-                          : w == 4 ? k_ekf_fact<4, true> : k_ekf_fact<5, true>)
-                       : (w == 1 ? k_ekf_fact<1, false> : w == 2 ? k_ekf_fact<2, false> : w == 3 ? k_ekf_fact<3, false>
-                          : w == 4 ? k_ekf_fact<4, false> : k_ekf_fact<5, false>);
-    hipLaunchKernelGGL(kf, dim3(1), dim3(kFactThreads), use_lds ? bytes : 0, s, Sup, r, res, res_stride, Linv, sc.y, Sg,
-                       use_lds, sc.chi2_gate, sc.chi2_thr, sc.dx + N);
+    auto *kf = R ? (use_lds ? ekf_fact_instance<true, true>(w) : ekf_fact_instance<false, true>(w))
+                 : (use_lds ? ekf_fact_instance<true, false>(w) : ekf_fact_instance<false, false>(w));
+    hipLaunchKernelGGL(kf, dim3(1), dim3(kFactThreads), use_lds ? bytes : 0, s, Sup, r, R, ldr, res, res_stride, Linv,
+                       sc.y, Sg, sc.chi2_gate, R ? chi2_thr : sc.chi2_thr, sc.dx + N);
   }
   // LDL^T of the r x r innovation covariance with the residual as an extra row: r^3/3 + r^2 FLOPs; the
-  // lower triangle and the residual read, the factor written
-  if (sc.kp) sc.kp->credit(KC_LDL, (double)r * r * r / 3.0 + (double)r * r, 8.0 * (1.5 * r * r + 2.0 * r));
+  // lower triangle (and R's) and the residual read, the factor written
+  if (sc.kp) sc.kp->credit(KC_LDL, (double)r * r * r / 3.0 + (double)r * r, 8.0 * ((R ? 2.0 : 1.5) * r * r + 2.0 * r));
   if (sc.chi2_gate) sc.gate = sc.chi2_gate;
+}
+
+// k_ekf_WP over the upper tile pairs of P with the factor launch_ekf_factor left in sc
+static void launch_ekf_WP(hipStream_t s, double *P, int ldp, int N, int r, EkfScratch &sc, const int *gate) {
+  const int nb = (N + 15) / 16;
+  const size_t lw = (size_t)(32 * (r | 1) + 1024) * sizeof(double);
+  hipLaunchKernelGGL(k_ekf_WP, dim3(nb * (nb + 1) / 2), dim3(256), lw, s, P, ldp, N, sc.M, r, sc.S, sc.y, sc.dx,
+                     sc.neg, gate, nb);
 }
 
 void launch_ekf_phaseB(hipStream_t s, double *P, int ldp, int N, int r, const double *res, int res_stride,
                        EkfScratch &sc) {
   launch_ekf_factor(s, N, r, res, res_stride, sc);
-  const int nb = (N + 15) / 16;
-  const size_t lw = (size_t)(32 * (r | 1) + 1024) * sizeof(double);
-  hipLaunchKernelGGL(k_ekf_WP, dim3(nb * (nb + 1) / 2), dim3(256), lw, s, P, ldp, N, sc.M, r, sc.S, sc.y, sc.dx,
-                     sc.neg, sc.gate, nb);
+  launch_ekf_WP(s, P, ldp, N, r, sc, sc.gate);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -844,13 +817,10 @@ __global__ void __launch_bounds__(kMSThreads) k_di_S(double *__restrict__ P, int
     for (int k = threadIdx.x; k < n; k += blockDim.x) hs[k] = hidx[k];
     __syncthreads();
     const int nt = (nup + 15) / 16;
-    int pair = b * (kMSThreads / 64) + wid, at = 0;
+    const int pair = b * (kMSThreads / 64) + wid;
     if (pair >= nt * (nt + 1) / 2) return;
-    while (pair >= nt - at) {
-      pair -= nt - at;
-      at++;
-    }
-    const int bt = at + pair;
+    int at, bt;
+    upper_pair(pair, nt, at, bt);
     const int ar = 16 * at + r16, br = 16 * bt + r16;
     const double *Ha = Hup + (size_t)min(ar, nup - 1) * ldh;
     const double *Tb = M + min(br, nup - 1);
@@ -973,10 +943,7 @@ static void di_candidate(hipStream_t s, double *P, int ldp, int Ni, const double
     hipLaunchKernelGGL(k_di_S<D>, dim3(nbG + nbX + 1), dim3(kMSThreads), ldsS, s, P, ldp, Ni, Hrow, ldh, nup, n, hidx,
                        s2, sc.M, sc.M3, Sup, fout, sc.chi2_gate, resout, nbG, nbX);
     launch_ekf_factor(s, N, nup, Hrow + D * (size_t)ldh + n, ldh, sc);
-    const int nb = (N + 15) / 16;
-    const size_t lw = (size_t)(32 * (nup | 1) + 1024) * sizeof(double);
-    hipLaunchKernelGGL(k_ekf_WP, dim3(nb * (nb + 1) / 2), dim3(256), lw, s, P, ldp, N, sc.M, nup, sc.S, sc.y, sc.dx,
-                       sc.neg, sc.chi2_gate, nb);
+    launch_ekf_WP(s, P, ldp, N, nup, sc, sc.chi2_gate);
   }
   launch_chain_apply(s, fout, sc.chi2_gate, sc.neg, sc.dx, clones, cv, ncl, cams, camv, ncam, calib_ext, calib_intr,
                      nullptr, 0, P, ldp, N, Ni, out, D);
@@ -1003,51 +970,19 @@ void launch_ekf_update(hipStream_t s, double *P, int ldp, int N, const double *H
 }
 
 // StateHelper::EKFUpdate (StateHelper.cpp:116-197) with the caller's dense R behind a chi2 gate on its own factor
-// (UpdaterUWB.cpp:67-79): phase A with s2 = 0, k_ekf_fact_R, k_ekf_WP behind the gate int sc.chi2_gate.  As many
-// launches as launch_ekf_update; M, the factor and the P update are that path's kernels.
+// (UpdaterUWB.cpp:67-79): phase A with s2 = 0, k_ekf_fact's dense-R instance, k_ekf_WP behind the gate int
+// sc.chi2_gate.  As many launches as launch_ekf_update; M, the factor and the P update are that path's kernels.
 void launch_ekf_update_R(hipStream_t s, double *P, int ldp, int N, const double *H, int ldh, int r, int n,
                          const int *hidx, const double *res, int res_stride, const double *R, int ldr, double chi2_thr,
                          EkfScratch &sc) {
-  int *gate = sc.chi2_gate;
-  if (!gate) throw std::runtime_error("EKF update with R: no gate in the scratch");
+  if (!sc.chi2_gate) throw std::runtime_error("EKF update with R: no gate in the scratch");
+  if (!R) throw std::runtime_error("EKF update with R: no R");
   if (r + 1 > kWaveMaxRows) throw std::runtime_error("direct EKF update with more rows than the factorization panel");
   if (ldr < r) throw std::runtime_error("EKF update: leading dimension of R below its row count");
   if (sc.Tall) throw std::runtime_error("EKF update with R: T of another H in the scratch");
   launch_ekf_phaseA(s, P, ldp, N, H, ldh, r, n, hidx, 0.0, sc);
-  static bool attrs = false;
-  if (!attrs) {
-    const void *fns[5] = {(const void *)k_ekf_fact_R<1, true>, (const void *)k_ekf_fact_R<2, true>,
-                          (const void *)k_ekf_fact_R<3, true>, (const void *)k_ekf_fact_R<4, true>,
-                          (const void *)k_ekf_fact_R<5, true>};
-    for (int k = 0; k < 5; k++)
-      if (set_dyn_lds(fns[k], kMaxDynLds) < kMaxDynLds)
-        throw std::runtime_error("dynamic LDS limit not granted for k_ekf_fact_R (" + std::to_string(k) + ")");
-    attrs = true;
-  }
-  const size_t bytes = ekf_small_lds_bytes(r);
-  const bool use_lds = bytes <= (size_t)kMaxDynLds;
-  double *Linv = sc.S, *Sup = sc.S + 2 * (size_t)r * r, *Sg = sc.S + 3 * (size_t)r * r;
-  {
-    KScope ks(sc.kp, KC_LDL);
-    const int w = panel_waves(r + 1);
-    auto *kf = use_lds ? (w == 1   ? k_ekf_fact_R<1, true>
-                          : w == 2 ? k_ekf_fact_R<2, true>
-                          : w == 3 ? k_ekf_fact_R<3, true>
-                          : w == 4 ? k_ekf_fact_R<4, true>
-                                   : k_ekf_fact_R<5, true>)
-                       : (w == 1   ? k_ekf_fact_R<1, false>
-                          : w == 2 ? k_ekf_fact_R<2, false>
-                          : w == 3 ? k_ekf_fact_R<3, false>
-                          : w == 4 ? k_ekf_fact_R<4, false>
-                                   : k_ekf_fact_R<5, false>);
-    hipLaunchKernelGGL(kf, dim3(1), dim3(kFactThreads), use_lds ? bytes : 0, s, Sup, r, R, ldr, res, res_stride, Linv,
-                       sc.y, Sg, gate, chi2_thr, sc.dx + N);
-  }
-  if (sc.kp) sc.kp->credit(KC_LDL, (double)r * r * r / 3.0 + (double)r * r, 8.0 * (2.0 * r * r + 2.0 * r));
-  const int nb = (N + 15) / 16;
-  const size_t lw = (size_t)(32 * (r | 1) + 1024) * sizeof(double);
-  hipLaunchKernelGGL(k_ekf_WP, dim3(nb * (nb + 1) / 2), dim3(256), lw, s, P, ldp, N, sc.M, r, sc.S, sc.y, sc.dx, sc.neg,
-                     (const int *)gate, nb);
+  launch_ekf_factor(s, N, r, res, res_stride, sc, R, ldr, chi2_thr);
+  launch_ekf_WP(s, P, ldp, N, r, sc, sc.chi2_gate);
 }
 
 }  // namespace uvhp

@@ -908,7 +908,7 @@ def aux_walk_p(P, ids, dims, sigma2, dt, ld=None):
 
 
 def position_update_p(P, imu_id, q_GtoI, p_IinG, s, Cm, z, R, aux_id=-1, chi2_thr=float("inf"), ld=None):
-    """uvio_hp_debug_position_update_p: k_fix_rows -> k_fix_M -> k_fix_update for one fix on a standalone covariance at
+    """uvio_hp_debug_position_update_p: k_fix_rows -> k_chain_M -> k_chain_update for one fix on a standalone covariance at
     the given pose.  The IMU pose's error columns start at imu_id, the lever arm s's at aux_id (< 0: a constant).
     Cm (r, 3), z (r), R (r, r') with r' >= r its leading dimension.  Returns (buf, dx, chi2, applied): the (N, ld)
     buffer as it came back (padding included); not applied: P unchanged, dx zeros."""
