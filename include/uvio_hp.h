@@ -43,6 +43,9 @@ extern "C" {
 #define UVIO_HP_MAX_CAMS 4
 #define UVIO_HP_MAX_ANCHORS 16
 #define UVIO_HP_AUX_MAX_DIM 8 /* scalars of one caller-defined state variable (uvio_hp_aux_add) */
+/* uvio_hp_feed_pose's mode: the rows of a pose fix */
+#define UVIO_HP_POSE_ORIENTATION 1 /* 3 rows: orientation only */
+#define UVIO_HP_POSE_FULL 2        /* 6 rows: orientation, then position */
 
 /* ---- option structs: the keys of estimator_config.yaml / kalibr_*.yaml / uwb_*.yaml ---- */
 
@@ -448,8 +451,9 @@ int uvio_hp_propagate(uvio_hp_t *h, double t);
  * UVIO_HP_E_NUMERIC (fatal, as everywhere): a negative covariance diagonal after an accepted update.
  * Serialized with the feeds.  When applied the odometry cache is republished, as after uvio_hp_msckf_update.
  * A state variable of the caller's own (a sensor bias, a lever arm) is added with uvio_hp_aux_add below and named
- * here like any other block.  A position fix can instead be buffered inside the frame and relinearized on the device
- * (uvio_hp_feed_position below); for any other model this call, after uvio_hp_propagate, is the one to use. */
+ * here like any other block.  A position fix or a pose fix can instead be buffered inside the frame and relinearized on
+ * the device (uvio_hp_feed_position, uvio_hp_feed_pose below); for any other model this call, after
+ * uvio_hp_propagate, is the one to use. */
 int uvio_hp_measurement_update(uvio_hp_t *h, int nvar, const int *ids, const int *sizes, const double *H, int ldh, int r,
                                const double *res, const double *R, int ldr, double chi2_thr, double *chi2, int *applied,
                                double *dx);
@@ -487,7 +491,20 @@ int uvio_hp_aux_add_from_measurement(uvio_hp_t *h, int dim, const double *val0, 
                                      const int *sizes, const double *H_x, int ldhx, const double *H_aux, int ldha,
                                      const double *res, const double *R, int ldr, const double *walk_sigma,
                                      int *handle);
-/* the variable's current covariance offset, its dimension and its value (val: dim doubles, may be NULL) */
+/* A JPL unit quaternion [x y z w] of the caller's own (a sensor's mounting rotation): 4 values, 3 error dimensions,
+ * updated as q <- dq(dtheta) (x) q with dq = normalize([dtheta / 2, 1]) (ov_type::JPLQuat::update), by every path that
+ * corrects the state: uvio_hp_measurement_update on its 3 columns, the frame's updates, UWB, zero-velocity, position
+ * and pose fixes.  Value and first estimate are set together.  q is normalized on entry; UVIO_HP_E_ARG when it is not
+ * finite or its norm lies outside [0.5, 2].  prior_cov is 3 x 3 (leading dimension ld >= 3, upper triangle read) over
+ * the error dtheta, walk_sigma[3] (NULL: a constant) in rad / sqrt(s).  The variable shows in
+ * uvio_hp_get_state_vector's meta as kind 7, size 3, and contributes 4 doubles to the value and first-estimate
+ * vectors; it counts 3 against max_aux_dim.  Every other refusal, their order (before any device work) and the
+ * sharding note are uvio_hp_aux_add's. */
+int uvio_hp_aux_add_quat(uvio_hp_t *h, const double q[4], const double *prior_cov, int ld, const double walk_sigma[3],
+                         int *handle);
+/* the variable's current covariance offset, its dimension and its value (val: dim doubles, may be NULL).  For a
+ * quaternion variable (uvio_hp_aux_add_quat) *dim = 3 and val receives 4 doubles: give val room for
+ * UVIO_HP_AUX_MAX_DIM doubles whenever the kind is not known. */
 int uvio_hp_aux_get(uvio_hp_t *h, int handle, int *id, int *dim, double *val);
 /* StateHelper::marginalize of the variable; the handle is dead afterwards */
 int uvio_hp_aux_remove(uvio_hp_t *h, int handle);
@@ -522,6 +539,41 @@ int uvio_hp_feed_position(uvio_hp_t *h, double t, int r, const double *C, const 
  * positive definite or a NaN chi2, or the aux handle was removed after queueing); the state is untouched.
  * *n is always written; UVIO_HP_E_CAPACITY when *n > cap (nothing else is written). */
 int uvio_hp_get_position_results(uvio_hp_t *h, double *t, double *chi2, int *status, int cap, int *n);
+
+/* ---- buffered pose fixes (motion capture, a dual-antenna GNSS/INS, a fiducial localizer) ----
+ * The rotation twin of uvio_hp_feed_position.  A sensor frame S is rigidly mounted on the body with the rotation q_ItoS
+ * and the lever arm s = p_SinI; an external system reports S's pose in the filter's global frame G: z_q = q_GtoS (JPL,
+ * [x y z w]) and z_p = p_SinG.  The caller aligns the frames, as for uvio_hp_feed_position (a filter started with
+ * uvio_hp_initialize_with_gt from the same system already has G equal to its frame).  With the JPL left error for both
+ * quaternions, R_GtoI = (I - [dtheta]x) R^_GtoI and R_ItoS = (I - [dphi]x) R^_ItoS, the prediction is
+ * q^_GtoS = q^_ItoS (x) q^_GtoI and p^ = p_IinG + R_GtoI^T s, and
+ *     orientation rows: dq = z_q (x) inv(q^_GtoS), negated when dq.w < 0; r_theta = 2 dq.xyz;
+ *                       H over [dtheta, dp, ds, dphi] = [ R^_ItoS | 0 | 0 | I ]
+ *     position rows:    r_p = z_p - p^;  H = [ -R_GtoI^T [s]x | I | R_GtoI^T | 0 ]
+ * mode UVIO_HP_POSE_ORIENTATION: r = 3 rows (z_p, p_SinI and the lever arm's columns are not used; z_p and p_SinI may
+ * be NULL); UVIO_HP_POSE_FULL: r = 6, orientation rows first.  R is dense r x r (leading dimension ldr, upper
+ * triangle read) in that row order: a mocap covariance couples rotation and translation.
+ * rot_handle > 0 names a live quaternion variable of uvio_hp_aux_add_quat as q_ItoS (the dphi block exists only then;
+ * q_ItoS is ignored and may be NULL), arm_handle > 0 a live 3-dimensional variable of uvio_hp_aux_add as s (the ds
+ * block exists only then and only in FULL mode; p_SinI is ignored).  Both are looked up at replay, value and covariance
+ * offset; a handle removed meanwhile refuses the fix (status 3).  z_q and q_ItoS are normalized on entry.
+ * Queueing, dropping, the gate (chi2_mult * uvio_hp_chi2_95(r), INFINITY: none), the status codes, the frame that ends
+ * in a zero-velocity update and the fatal UVIO_HP_E_NUMERIC are uvio_hp_feed_position's, and the queue is the same
+ * one: 256 entries across both kinds.  Replay is merged in ascending time with the UWB messages and the position
+ * fixes; at one timestamp the UWB message goes first, then the fixes of both kinds in feed order, each linearized at
+ * the state the previous one left.  Consecutive pose fixes of one timestamp run as one device chain with one readback
+ * per 8; a change of kind ends a chain.
+ * UVIO_HP_E_ARG, before anything is stored: null pointers (z_p in FULL mode among them), a mode that is neither
+ * constant, ldr < r, a non-finite t, z_p, read triangle of R or p_SinI, a z_q or q_ItoS that is not finite or whose norm
+ * lies outside [0.5, 2], a diagonal of R that is not positive, a chi2_mult that is not positive (or NaN), a rot_handle
+ * that is dead or not a quaternion variable, an arm_handle that is dead or not an additive 3-vector.
+ * UVIO_HP_E_CAPACITY: 256 fixes are already queued. */
+int uvio_hp_feed_pose(uvio_hp_t *h, double t, int mode, const double z_q[4], const double *z_p, const double *R, int ldr,
+                      const double q_ItoS[4], int rot_handle, const double *p_SinI, int arm_handle, double chi2_mult,
+                      int *queued);
+/* The pose fixes consumed by the last camera or simulation feed, in processing order, with
+ * uvio_hp_get_position_results' conventions and status codes (that call keeps reporting position fixes only). */
+int uvio_hp_get_pose_results(uvio_hp_t *h, double *t, double *chi2, int *status, int cap, int *n);
 
 /* ---- feature-sharded MSCKF update across GPUs (BASELINE.json configs 4-5) ----
  * One process per GPU, each with its own handle fed the same measurement stream (the filter state is
@@ -607,6 +659,15 @@ int uvio_hp_aux_walk_p(double *P, int N, int ld, int ntab, const int *ids, const
 int uvio_hp_debug_position_update_p(double *P, int N, int ld, int imu_id, const double *q, const double *p, int aux_id,
                                     const double *s, int r, const double *C, const double *z, const double *R, int ldr,
                                     double chi2_thr, double *dx, double *chi2, int *applied);
+/* The three kernels of the buffered pose-fix chain (uvio_hp_feed_pose) for one fix on a caller's host covariance, with
+ * uvio_hp_debug_position_update_p's conventions: q[4] = q_GtoI, p[3] = p_IinG at imu_id, s[3] the lever arm whose 3
+ * columns start at arm_id, q_ItoS[4] the mounting rotation whose 3 error columns start at rot_id (either id < 0: a
+ * constant; the blocks must not overlap; N >= 6 plus the blocks used).  mode, z_q, z_p, R, ldr as for
+ * uvio_hp_feed_pose; an orientation-only fix uses no lever-arm columns. */
+int uvio_hp_debug_pose_update_p(double *P, int N, int ld, int imu_id, const double *q, const double *p, int arm_id,
+                                const double *s, int rot_id, const double *q_ItoS, int mode, const double *z_q,
+                                const double *z_p, const double *R, int ldr, double chi2_thr, double *dx, double *chi2,
+                                int *applied);
 /* boost::math::quantile(chi_squared(dof), 0.95), the table every reference updater multiplies its chi2_multipler
  * into (UpdaterMSCKF.cpp:52-55, UpdaterSLAM.cpp:55-58, UpdaterZeroVelocity.cpp:59-62, UpdaterUWB.h:33-36), for
  * dof 1 .. 999; UVIO_HP_E_ARG outside that range. */

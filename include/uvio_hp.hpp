@@ -17,6 +17,8 @@
  *   Manager::add_state             <- StateHelper::set_initial_covariance (StateHelper.cpp:199) for a variable of the caller's
  *   Manager::add_state_from_measurement <- StateHelper::initialize_invertible (StateHelper.cpp:484)
  *   Manager::feed_position         <- the UWB buffer-and-replay of UVioManager.cpp:178-188 for a position fix
+ *   Manager::feed_pose             <- the same for a pose fix (orientation rows, then position rows)
+ *   Manager::add_quat_state        <- set_initial_covariance for a JPL quaternion of the caller's (ov_type::JPLQuat)
  */
 #ifndef UVIO_HP_HPP
 #define UVIO_HP_HPP
@@ -24,6 +26,7 @@
 #include <array>
 #include <cmath>
 #include <cstdint>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -440,16 +443,29 @@ class Manager {
                                            walk_sigma.empty() ? nullptr : walk_sigma.data(), &handle));
     return handle;
   }
+  // A JPL unit quaternion [x y z w] of the caller's own (a mounting rotation): 3 error dimensions, updated as
+  // q <- dq(dtheta) (x) q; prior_cov 3 x 3 row-major over dtheta, walk_sigma in rad / sqrt(s) (empty: a constant).
+  // q is normalized on entry.  Returns the handle; aux_state(handle).value then holds 4 doubles.
+  int add_quat_state(const std::array<double, 4> &q, const std::array<double, 9> &prior_cov,
+                     const std::vector<double> &walk_sigma = {}) {
+    if (!walk_sigma.empty() && walk_sigma.size() != 3) throw Error(UVIO_HP_E_ARG, "add_quat_state: size mismatch");
+    int handle = 0;
+    check(uvio_hp_aux_add_quat(h_, q.data(), prior_cov.data(), 3, walk_sigma.empty() ? nullptr : walk_sigma.data(),
+                               &handle));
+    return handle;
+  }
   struct AuxState {
     int id = 0;  // the covariance offset NOW: it moves when clones / landmarks in front are marginalized
-    std::vector<double> value;
+    std::vector<double> value;  // a quaternion variable: 4 values over 3 error dimensions
   };
   AuxState aux_state(int handle) const {
     AuxState a;
     int dim = 0;
     double v[UVIO_HP_AUX_MAX_DIM];
+    for (double &x : v) x = std::numeric_limits<double>::quiet_NaN();
     check(uvio_hp_aux_get(h_, handle, &a.id, &dim, v));
-    a.value.assign(v, v + dim);
+    // a quaternion variable reports dim = 3 and writes 4 doubles (values are always finite)
+    a.value.assign(v, v + ((dim == 3 && v[3] == v[3]) ? 4 : dim));
     return a;
   }
   // marginalizes the variable; the handle is dead afterwards
@@ -497,6 +513,33 @@ class Manager {
     std::vector<double> t((size_t)n), c((size_t)n);
     std::vector<int> s((size_t)n);
     if (n > 0) check(uvio_hp_get_position_results(h_, t.data(), c.data(), s.data(), n, &n));
+    std::vector<PositionResult> out((size_t)n);
+    for (size_t k = 0; k < out.size(); k++) out[k].t = t[k], out[k].chi2 = c[k], out[k].status = s[k];
+    return out;
+  }
+
+  // ---- buffered pose fixes (uvio_hp_feed_pose): the sensor frame S's pose in G, z_q = q_GtoS and z_p = p_SinG ----
+  // R row-major r x r (r = 3: orientation only, z_p unused; r = 6: orientation rows, then position rows), the mounting
+  // rotation q_ItoS constant or, with rot_handle > 0, a variable of add_quat_state; the lever arm p_SinI constant or,
+  // with arm_handle > 0, a 3-scalar variable of add_state.  True when queued.
+  bool feed_pose(double t, const std::array<double, 4> &z_q, const std::array<double, 3> &z_p, const std::vector<double> &R,
+                 const std::array<double, 4> &q_ItoS = {0.0, 0.0, 0.0, 1.0}, int rot_handle = 0,
+                 const std::array<double, 3> &p_SinI = {0.0, 0.0, 0.0}, int arm_handle = 0, double chi2_mult = 1.0) {
+    if (R.size() != 9 && R.size() != 36) throw Error(UVIO_HP_E_ARG, "feed_pose: R is neither 3 x 3 nor 6 x 6");
+    const bool full = R.size() == 36;
+    int queued = 0;
+    check(uvio_hp_feed_pose(h_, t, full ? UVIO_HP_POSE_FULL : UVIO_HP_POSE_ORIENTATION, z_q.data(), z_p.data(), R.data(),
+                            full ? 6 : 3, q_ItoS.data(), rot_handle, p_SinI.data(), arm_handle, chi2_mult, &queued));
+    return queued != 0;
+  }
+  // the pose fixes the last camera / simulation feed consumed, in processing order
+  std::vector<PositionResult> pose_results() const {
+    int n = 0;
+    const int rc = uvio_hp_get_pose_results(h_, nullptr, nullptr, nullptr, 0, &n);
+    if (rc != UVIO_HP_E_CAPACITY) check(rc);
+    std::vector<double> t((size_t)n), c((size_t)n);
+    std::vector<int> s((size_t)n);
+    if (n > 0) check(uvio_hp_get_pose_results(h_, t.data(), c.data(), s.data(), n, &n));
     std::vector<PositionResult> out((size_t)n);
     for (size_t k = 0; k < out.size(); k++) out[k].t = t[k], out[k].chi2 = c[k], out[k].status = s[k];
     return out;

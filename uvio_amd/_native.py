@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("UVIO_HP_LIB", os.path.join(ROOT, "uvio_amd", "libuvio
 MAX_CAMS = 4
 MAX_ANCHORS = 16
 AUX_MAX_DIM = 8
+POSE_ORIENTATION, POSE_FULL = 1, 2  # uvio_hp_feed_pose's mode
 
 OK = 0
 E_ARG, E_STATE, E_DEVICE, E_NUMERIC, E_CONFIG, E_ORDER, E_CAPACITY, E_INTERNAL = -1, -2, -3, -4, -5, -6, -7, -8
@@ -189,6 +190,11 @@ SIGNATURES = [
     ("aux_append_p", _I, [_P(_D), _I, _I, _I, _P(_D), _I]),
     ("aux_init_p", _I, [_P(_D), _I, _I, _I, _P(_I), _I, _P(_D), _I, _P(_D), _P(_D), _P(_D), _I]),
     ("aux_walk_p", _I, [_P(_D), _I, _I, _I, _P(_I), _P(_I), _P(_D), _D]),
+    ("aux_add_quat", _I, [C.c_void_p, _P(_D), _P(_D), _I, _P(_D), _P(_I)]),
+    ("feed_pose", _I, [C.c_void_p, _D, _I, _P(_D), _P(_D), _P(_D), _I, _P(_D), _I, _P(_D), _I, _D, _P(_I)]),
+    ("get_pose_results", _I, [C.c_void_p, _P(_D), _P(_D), _P(_I), _I, _P(_I)]),
+    ("debug_pose_update_p", _I, [_P(_D), _I, _I, _I, _P(_D), _P(_D), _I, _P(_D), _I, _P(_D), _I, _P(_D), _P(_D), _P(_D),
+                                 _I, _D, _P(_D), _P(_D), _P(_I)]),
     ("feed_position", _I, [C.c_void_p, _D, _I, _P(_D), _P(_D), _P(_D), _I, _P(_D), _I, _D, _P(_I)]),
     ("get_position_results", _I, [C.c_void_p, _P(_D), _P(_D), _P(_I), _I, _P(_I)]),
     ("debug_position_update_p", _I, [_P(_D), _I, _I, _I, _P(_D), _P(_D), _I, _P(_D), _I, _P(_D), _P(_D), _P(_D), _I, _D,

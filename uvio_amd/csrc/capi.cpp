@@ -392,6 +392,11 @@ int uvio_hp_aux_add(uvio_hp_t *h, int dim, const double *val, const double *prio
   if (!h) return UVIO_HP_E_ARG;
   HP_FEED(h, h->e->api_aux_add(dim, val, prior_cov, ld, walk_sigma, handle))
 }
+int uvio_hp_aux_add_quat(uvio_hp_t *h, const double q[4], const double *prior_cov, int ld, const double walk_sigma[3],
+                         int *handle) {
+  if (!h) return UVIO_HP_E_ARG;
+  HP_FEED(h, h->e->api_aux_add_quat(q, prior_cov, ld, walk_sigma, handle))
+}
 int uvio_hp_aux_add_from_measurement(uvio_hp_t *h, int dim, const double *val0, int nvar, const int *ids,
                                      const int *sizes, const double *H_x, int ldhx, const double *H_aux, int ldha,
                                      const double *res, const double *R, int ldr, const double *walk_sigma,
@@ -468,6 +473,39 @@ int uvio_hp_debug_position_update_p(double *P, int N, int ld, int imu_id, const 
   try {
     return Engine::position_update_standalone(P, N, ld, imu_id, q, p, aux_id, s, r, C, z, R, ldr, chi2_thr, dx, chi2,
                                               applied);
+  } catch (const HpError &ex) {
+    return ex.code;
+  } catch (...) {
+    return UVIO_HP_E_DEVICE;
+  }
+}
+
+// ---- buffered pose fixes (engine_update.cpp) ----
+int uvio_hp_feed_pose(uvio_hp_t *h, double t, int mode, const double z_q[4], const double *z_p, const double *R, int ldr,
+                      const double q_ItoS[4], int rot_handle, const double *p_SinI, int arm_handle, double chi2_mult,
+                      int *queued) {
+  if (!h) return UVIO_HP_E_ARG;
+  HP_FEED(h, h->e->feed_pose(t, mode, z_q, z_p, R, ldr, q_ItoS, rot_handle, p_SinI, arm_handle, chi2_mult, queued))
+}
+int uvio_hp_get_pose_results(uvio_hp_t *h, double *t, double *chi2, int *status, int cap, int *n) {
+  if (!h || !n) return UVIO_HP_E_ARG;
+  const auto &v = h->e->pose_results();
+  *n = (int)v.size();
+  if (*n > cap) return UVIO_HP_E_CAPACITY;
+  for (int k = 0; k < *n; k++) {
+    if (t) t[k] = v[(size_t)k].t;
+    if (chi2) chi2[k] = v[(size_t)k].chi2;
+    if (status) status[k] = v[(size_t)k].status;
+  }
+  return 0;
+}
+int uvio_hp_debug_pose_update_p(double *P, int N, int ld, int imu_id, const double *q, const double *p, int arm_id,
+                                const double *s, int rot_id, const double *q_ItoS, int mode, const double *z_q,
+                                const double *z_p, const double *R, int ldr, double chi2_thr, double *dx, double *chi2,
+                                int *applied) {
+  try {
+    return Engine::pose_update_standalone(P, N, ld, imu_id, q, p, arm_id, s, rot_id, q_ItoS, mode, z_q, z_p, R, ldr,
+                                          chi2_thr, dx, chi2, applied);
   } catch (const HpError &ex) {
     return ex.code;
   } catch (...) {

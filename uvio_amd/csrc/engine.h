@@ -30,7 +30,8 @@
 namespace uvhp {
 
 // V_AUX: a caller-defined additive vector (uvio_hp_aux_add), updated like V_VEC
-enum VKind { V_IMU = 0, V_VEC = 1, V_QUAT = 2, V_POSE = 3, V_LANDMARK = 4, V_ANCHOR = 5, V_AUX = 6 };
+// V_AUX_QUAT: a caller-defined JPL quaternion (uvio_hp_aux_add_quat), updated like V_QUAT
+enum VKind { V_IMU = 0, V_VEC = 1, V_QUAT = 2, V_POSE = 3, V_LANDMARK = 4, V_ANCHOR = 5, V_AUX = 6, V_AUX_QUAT = 7 };
 
 // ov_type::Type bookkeeping + value / first estimate
 struct Var {
@@ -467,6 +468,8 @@ double ekf_bytes(double N, double n, double r);
 bool ekf_R_inputs_finite(const double *H, int ldh, int r, int n, const double *res, const double *R, int ldr);
 // the upper triangle of a caller's d x d matrix (ld) is finite (and, with pos_diag, its diagonal positive)
 bool aux_upper_ok(const double *A, int ld, int d, bool pos_diag);
+// a finite quaternion whose norm lies in [0.5, 2], normalized into out
+bool unit_quat_ok(const double *q, double *out);
 // inv (d x d packed) <- A^-1 (d x d, ld lda) by Gauss-Jordan with partial pivoting; false when an entry is not
 // finite or a pivot is not above d * 2^-52 * max |A| (singular)
 bool aux_inverse(const double *A, int lda, int d, double *inv);
@@ -491,6 +494,10 @@ class Engine {
     int status;  // 0 applied, 1 gated, 2 dropped, 3 refused
   };
   const std::vector<FixResult> &position_results() const { return fix_results_; }
+  // uvio_hp_feed_pose: one pose fix into the same queue (past_fix_), replayed in feed order with the position fixes
+  int feed_pose(double t, int mode, const double *z_q, const double *z_p, const double *R, int ldr, const double *q_ItoS,
+                int rot_handle, const double *p_SinI, int arm_handle, double chi2_mult, int *queued);
+  const std::vector<FixResult> &pose_results() const { return pose_results_; }
   Tracker *tracker() { return tracker_.get(); }
   int init_anchors(int n, const uvio_hp_anchor_t *a);
   // HIP's current device is per host thread: every C-ABI entry binds the engine's device first, so a handle
@@ -542,6 +549,11 @@ class Engine {
                                         int aux_id, const double *s, int r, const double *C, const double *z,
                                         const double *R, int ldr, double chi2_thr, double *dx, double *chi2,
                                         int *applied);
+  // the three kernels of the pose-fix chain on a caller's host covariance (uvio_hp_debug_pose_update_p)
+  static int pose_update_standalone(double *P, int N, int ld, int imu_id, const double *q, const double *p, int arm_id,
+                                    const double *s, int rot_id, const double *q_ItoS, int mode, const double *z_q,
+                                    const double *z_p, const double *R, int ldr, double chi2_thr, double *dx,
+                                    double *chi2, int *applied);
 
  private:
   uvio_hp_options_t o_;
@@ -634,10 +646,15 @@ class Engine {
     double s[3];              // the constant lever arm (aux <= 0)
     int aux;                  // aux handle, <= 0: constant lever arm
     double thr;
+    // a pose fix (uvio_hp_feed_pose) when pose_r != 0: z holds z_p, s and aux the lever arm, and
+    int pose_r = 0;            // 3: orientation only, 6: orientation then position
+    double zq[4], qS[4];       // z_q = q_GtoS and the constant q_ItoS (rot <= 0), both unit norm
+    int rot = 0;               // aux handle of the mounting rotation, <= 0: constant
+    double Rp[36];             // pose_r x pose_r at leading dimension kChainMaxRows, symmetric
   };
   std::map<double, std::vector<FixMeas>> past_fix_;
   int fix_queued_ = 0;
-  std::vector<FixResult> fix_results_;
+  std::vector<FixResult> fix_results_, pose_results_;
   uvio_hp_timing_t timing_{};
   std::vector<double> chi2_table_;
   ShardComm shard_;
@@ -697,6 +714,7 @@ class Engine {
   // caller-defined state variables (include/uvio_hp.h uvio_hp_aux_*): appended at N_ on the device
   // (launch_aux_append / launch_aux_init), removed by marginalize
   int api_aux_add(int dim, const double *val, const double *prior, int ld, const double *walk_sigma, int *handle);
+  int api_aux_add_quat(const double *q, const double *prior, int ld, const double *walk_sigma, int *handle);
   int api_aux_add_from_measurement(int dim, const double *val0, int nvar, const int *ids, const int *sizes,
                                    const double *H_x, int ldhx, const double *H_aux, int ldha, const double *res,
                                    const double *R, int ldr, const double *walk_sigma, int *handle);
@@ -778,7 +796,7 @@ class Engine {
   int aux_next_ = 1, aux_dims_ = 0, aux_walkers_ = 0;
   // the checks every aux_add shares (before any device work); returns walk_sigma^2 in s2
   void aux_check_new(const char *who, int dim, const double *walk_sigma, double *s2) const;
-  int aux_register(int dim, const double *val, const double *s2);
+  int aux_register(int dim, const double *val, const double *s2, bool quat = false);
   // P[i][i] += walk_sigma^2 * dt over every walking aux component, one launch (k_aux_walk); called wherever
   // timestamp_ advances by dt
   void aux_walk(double dt);
@@ -896,7 +914,10 @@ class Engine {
   int uwb_update_message(const std::vector<std::pair<size_t, double>> &ranges);
   // The fixes of one timestamp on the current state as device chains of up to kFixMaxChain fixes, one readback each:
   // an aux lever arm's covariance offset and value are resolved here; one FixResult per fix is appended
-  void fix_update_chain(double t, const std::vector<FixMeas> &fixes);
+  void fix_update_chain(double t, const FixMeas *fixes, size_t n);
+  // The same for a run of pose fixes (k_pose_rows): an aux lever arm and an aux mounting rotation are resolved here;
+  // one FixResult per fix is appended to pose_results_
+  void pose_update_chain(double t, const FixMeas *fixes, size_t n);
   // One measurement chain of n <= kChainMaxSteps steps on d_.stream: enqueue(j, prev, row, region) puts step j's
   // three launches there (prev: step j-1's region, null for j = 0).  Then one readback of every region and one
   // wait; returns the pinned regions (step j's at j * d_.mchain_stride doubles: chain_header, then dx).

@@ -243,10 +243,10 @@ void Engine::aux_check_new(const char *who, int dim, const double *walk_sigma, d
 }
 
 // the variable enters vars_ at offset N_ (its covariance rows / columns are already enqueued)
-int Engine::aux_register(int dim, const double *val, const double *s2) {
+int Engine::aux_register(int dim, const double *val, const double *s2, bool quat) {
   ++p_epoch_;
-  VarP v = std::make_shared<Var>(V_AUX, dim, dim);
-  for (int k = 0; k < dim; k++) v->val[k] = v->fej[k] = val[k];
+  VarP v = quat ? std::make_shared<Var>(V_AUX_QUAT, 3, 4) : std::make_shared<Var>(V_AUX, dim, dim);
+  for (int k = 0; k < v->vlen; k++) v->val[k] = v->fej[k] = val[k];
   v->id = N_;
   N_ += dim;
   vars_.push_back(v);
@@ -280,6 +280,30 @@ int Engine::api_aux_add(int dim, const double *val, const double *prior, int ld,
   stage_flush();
   launch_aux_append(d_.stream, d_.P, d_.ldp, N_, dim, dpr);
   *handle = aux_register(dim, val, s2);
+  return 0;
+}
+
+// A JPL unit quaternion of the caller's (3 error dimensions, q <- dq(dtheta) (x) q): aux_add's refusals in aux_add's
+// order, the same append kernel at dim = 3, the same walk
+int Engine::api_aux_add_quat(const double *q, const double *prior, int ld, const double *walk_sigma, int *handle) {
+  stage_ = "aux_add_quat";
+  if (!is_initialized_) throw HpError(UVIO_HP_E_STATE, "aux_add_quat before initialization");
+  if (!q || !prior || !handle) return UVIO_HP_E_ARG;
+  double s2[UVIO_HP_AUX_MAX_DIM];
+  aux_check_new("aux_add_quat", 3, walk_sigma, s2);
+  if (ld < 3) throw HpError(UVIO_HP_E_ARG, "aux_add_quat: leading dimension below the row length");
+  double qn[4];
+  if (!unit_quat_ok(q, qn)) throw HpError(UVIO_HP_E_ARG, "aux_add_quat: q is not finite or its norm is outside [0.5, 2]");
+  if (!aux_upper_ok(prior, ld, 3, true))
+    throw HpError(UVIO_HP_E_ARG, "aux_add_quat: the upper triangle of prior_cov must be finite with a positive diagonal");
+  void *hv = nullptr;
+  const double *dpr = (const double *)stage_reserve(sizeof(double) * 9, &hv);
+  double *hp = (double *)hv;
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) hp[i * 3 + j] = j >= i ? prior[(size_t)i * ld + j] : 0.0;
+  stage_flush();
+  launch_aux_append(d_.stream, d_.P, d_.ldp, N_, 3, dpr);
+  *handle = aux_register(3, qn, s2, true);
   return 0;
 }
 
@@ -353,7 +377,7 @@ int Engine::api_aux_get(int handle, int *id, int *dim, double *val) {
   const Var &v = *it->second.v;
   *id = v.id;
   *dim = v.size;
-  if (val) std::memcpy(val, v.val, sizeof(double) * v.size);
+  if (val) std::memcpy(val, v.val, sizeof(double) * v.vlen);  // a quaternion variable: dim 3, 4 values
   return 0;
 }
 

@@ -11,7 +11,7 @@ namespace uvhp {
 
 // ---- Type::update family ----
 void Var::update(const double *dx) {
-  if (kind == V_IMU || kind == V_POSE || kind == V_QUAT) {
+  if (kind == V_IMU || kind == V_POSE || kind == V_QUAT || kind == V_AUX_QUAT) {
     quat_boxplus(val, dx);
     for (int i = 3; i < size; i++) val[i + 1] += dx[i];
   } else {
@@ -1147,6 +1147,65 @@ int Engine::position_update_standalone(double *P, int N, int ld, int imu_id, con
     HP_HIP(hipMemcpyAsync(dst, &st, sizeof(st), hipMemcpyHostToDevice, sm));
     HP_HIP(hipMemsetAsync(dreg, 0, sizeof(double) * reg.size(), sm));
     launch_fix_rows(sm, dst, 0, nullptr, drow, region);
+    launch_chain_M(sm, dP, ld, N, drow, r, dM);
+    launch_chain_update(sm, dP, ld, N, dM, drow, r, false, region);
+    HP_HIP(hipMemcpyAsync(reg.data(), dreg, sizeof(double) * reg.size(), hipMemcpyDeviceToHost, sm));
+  });
+  if (rc) return rc;
+  const DChainRegion g = chain_header(reg.data());
+  *chi2 = g.chi2;
+  *applied = g.accepted != 0.0 ? 1 : 0;
+  for (int i = 0; i < N; i++) dx[i] = *applied ? reg[kChainHeader + i] : 0.0;
+  if (g.extra != 0.0) return UVIO_HP_E_ARG;  // refused: S is not positive definite, nothing was applied
+  if (*applied && g.neg > 0) return UVIO_HP_E_NUMERIC;
+  return 0;
+}
+
+// One pose fix through k_pose_rows -> k_chain_M -> k_chain_update (Engine::pose_update_chain's launches for a chain of
+// one) on a caller's covariance at a caller's pose, lever arm and mounting rotation
+int Engine::pose_update_standalone(double *P, int N, int ld, int imu_id, const double *q, const double *p, int arm_id,
+                                   const double *s, int rot_id, const double *q_ItoS, int mode, const double *z_q,
+                                   const double *z_p, const double *R, int ldr, double chi2_thr, double *dx,
+                                   double *chi2, int *applied) {
+  if (!P || !q || !p || !s || !q_ItoS || !z_q || !R || !dx || !chi2 || !applied) return UVIO_HP_E_ARG;
+  if (mode != UVIO_HP_POSE_ORIENTATION && mode != UVIO_HP_POSE_FULL) return UVIO_HP_E_ARG;
+  const bool full = mode == UVIO_HP_POSE_FULL;
+  const int r = full ? 6 : 3;
+  if ((full && !z_p) || ldr < r || N < 6 || ld < N || !(chi2_thr > 0.0)) return UVIO_HP_E_ARG;
+  if (imu_id < 0 || (long long)imu_id + 6 > N) return UVIO_HP_E_ARG;
+  auto clear = [&](int id, int lo, int len) { return (long long)id + 3 <= N && (id + 3 <= lo || id >= lo + len); };
+  if (arm_id >= 0 && !clear(arm_id, imu_id, 6)) return UVIO_HP_E_ARG;
+  if (rot_id >= 0 && (!clear(rot_id, imu_id, 6) || (arm_id >= 0 && !clear(rot_id, arm_id, 3)))) return UVIO_HP_E_ARG;
+  if (!aux_upper_ok(R, ldr, r, true)) return UVIO_HP_E_ARG;
+  DPoseState st{};
+  bool finite = true;
+  for (int k = 0; k < 4; k++) finite = finite && std::isfinite(st.q[k] = q[k]);
+  for (int k = 0; k < 3; k++) finite = finite && std::isfinite(st.p[k] = p[k]) && std::isfinite(st.s[0][k] = s[k]);
+  if (full)
+    for (int k = 0; k < 3; k++) finite = finite && std::isfinite(st.zp[0][k] = z_p[k]);
+  if (!finite || !unit_quat_ok(q_ItoS, st.qS[0]) || !unit_quat_ok(z_q, st.zq[0])) return UVIO_HP_E_ARG;
+  for (int i = 0; i < r; i++)
+    for (int j = i; j < r; j++) st.R[0][kChainMaxRows * i + j] = st.R[0][kChainMaxRows * j + i] = R[(size_t)i * ldr + j];
+  st.thr[0] = chi2_thr;
+  st.r[0] = r;
+  st.id_arm[0] = (arm_id >= 0 && full) ? arm_id : -1;  // an orientation-only fix has no lever-arm columns
+  st.id_rot[0] = rot_id >= 0 ? rot_id : -1;
+  st.id_imu = imu_id;
+  st.nf = 1;
+  DevBuf<DPoseState> dst;
+  DevBuf<DChainRow> drow;
+  DevBuf<double> dM;
+  DevBuf<unsigned char> dreg;
+  std::vector<double> reg((size_t)N + kChainHeader, 0.0);
+  const int rc = aux_standalone_run(P, (size_t)N, ld, [&](hipStream_t sm, double *dP) {
+    dst = DevBuf<DPoseState>(1);
+    drow = DevBuf<DChainRow>(1);
+    dM = DevBuf<double>((size_t)kChainMaxRows * N);
+    dreg = DevBuf<unsigned char>(sizeof(double) * reg.size());
+    DChainRegion *region = chain_region(dreg, reg.size(), 0);
+    HP_HIP(hipMemcpyAsync(dst, &st, sizeof(st), hipMemcpyHostToDevice, sm));
+    HP_HIP(hipMemsetAsync(dreg, 0, sizeof(double) * reg.size(), sm));
+    launch_pose_rows(sm, dst, 0, nullptr, drow, region);
     launch_chain_M(sm, dP, ld, N, drow, r, dM);
     launch_chain_update(sm, dP, ld, N, dM, drow, r, false, region);
     HP_HIP(hipMemcpyAsync(reg.data(), dreg, sizeof(double) * reg.size(), hipMemcpyDeviceToHost, sm));

@@ -174,12 +174,85 @@ int Engine::feed_position(double t, int r, const double *C, const double *z, con
   if (aux_handle > 0) {
     auto it = aux_.find(aux_handle);
     if (it == aux_.end()) throw HpError(UVIO_HP_E_ARG, std::string(who) + "no live aux variable has this handle");
-    if (it->second.v->size != 3) throw HpError(UVIO_HP_E_ARG, std::string(who) + "the aux variable is not a 3-vector");
+    if (it->second.v->kind != V_AUX || it->second.v->size != 3)
+      throw HpError(UVIO_HP_E_ARG, std::string(who) + "the aux variable is not a 3-vector");
   }
   if (fix_queued_ >= kFixQueueMax)
     throw HpError(UVIO_HP_E_CAPACITY, std::string(who) + "more than " + std::to_string(kFixQueueMax) + " fixes queued");
   m.r = r;
   m.aux = aux_handle > 0 ? aux_handle : 0;
+  m.thr = chi2_mult * chi2_table_[r];
+  past_fix_[t].push_back(m);
+  fix_queued_++;
+  *queued = 1;
+  return 0;
+}
+
+// a finite quaternion whose norm lies in [0.5, 2], normalized into out (uvio_hp_aux_add_quat, uvio_hp_feed_pose)
+bool unit_quat_ok(const double *q, double *out) {
+  double n2 = 0.0;
+  for (int k = 0; k < 4; k++) {
+    if (!std::isfinite(q[k])) return false;
+    n2 += q[k] * q[k];
+  }
+  const double n = std::sqrt(n2);
+  if (!(n >= 0.5 && n <= 2.0)) return false;
+  for (int k = 0; k < 4; k++) out[k] = q[k] / n;
+  return true;
+}
+
+// A pose fix (kernels.h DPoseState) for the next frame's replay, into feed_position's queue.  Every refusal comes
+// before anything is stored.
+int Engine::feed_pose(double t, int mode, const double *z_q, const double *z_p, const double *R, int ldr,
+                      const double *q_ItoS, int rot_handle, const double *p_SinI, int arm_handle, double chi2_mult,
+                      int *queued) {
+  stage_ = "feed_pose";
+  const std::string who = "feed_pose: ";
+  if (!queued) throw HpError(UVIO_HP_E_ARG, who + "null pointer");
+  *queued = 0;
+  if (mode != UVIO_HP_POSE_ORIENTATION && mode != UVIO_HP_POSE_FULL)
+    throw HpError(UVIO_HP_E_ARG, who + "mode is neither UVIO_HP_POSE_ORIENTATION nor UVIO_HP_POSE_FULL");
+  const bool full = mode == UVIO_HP_POSE_FULL;
+  const int r = full ? 6 : 3;
+  if (!z_q || !R || (full && !z_p) || (rot_handle <= 0 && !q_ItoS) || (full && arm_handle <= 0 && !p_SinI))
+    throw HpError(UVIO_HP_E_ARG, who + "null pointer");
+  if (ldr < r) throw HpError(UVIO_HP_E_ARG, who + "leading dimension below the row length");
+  if (!(chi2_mult > 0.0)) throw HpError(UVIO_HP_E_ARG, who + "chi2_mult must be positive");
+  FixMeas m{};
+  bool finite = std::isfinite(t);
+  constexpr int ldm = kChainMaxRows;
+  for (int i = 0; i < r; i++)
+    for (int j = i; j < r; j++)
+      finite = finite && std::isfinite(m.Rp[ldm * i + j] = m.Rp[ldm * j + i] = R[(size_t)i * ldr + j]);
+  if (full)
+    for (int k = 0; k < 3; k++) finite = finite && std::isfinite(m.z[k] = z_p[k]);
+  if (full && arm_handle <= 0)
+    for (int k = 0; k < 3; k++) finite = finite && std::isfinite(m.s[k] = p_SinI[k]);
+  if (!finite) throw HpError(UVIO_HP_E_ARG, who + "t, z_p, the upper triangle of R or p_SinI is not finite");
+  if (!unit_quat_ok(z_q, m.zq)) throw HpError(UVIO_HP_E_ARG, who + "z_q is not finite or its norm is outside [0.5, 2]");
+  m.qS[3] = 1.0;
+  if (rot_handle <= 0 && !unit_quat_ok(q_ItoS, m.qS))
+    throw HpError(UVIO_HP_E_ARG, who + "q_ItoS is not finite or its norm is outside [0.5, 2]");
+  for (int i = 0; i < r; i++)
+    if (!(m.Rp[(ldm + 1) * i] > 0.0)) throw HpError(UVIO_HP_E_ARG, who + "the diagonal of R must be positive");
+  if (!is_initialized_ || timestamp_ >= t) return 0;  // feed_uwb's behaviour, as in feed_position
+  if (rot_handle > 0) {
+    auto it = aux_.find(rot_handle);
+    if (it == aux_.end()) throw HpError(UVIO_HP_E_ARG, who + "no live aux variable has the rotation handle");
+    if (it->second.v->kind != V_AUX_QUAT)
+      throw HpError(UVIO_HP_E_ARG, who + "the rotation handle is not a quaternion variable");
+  }
+  if (arm_handle > 0) {
+    auto it = aux_.find(arm_handle);
+    if (it == aux_.end()) throw HpError(UVIO_HP_E_ARG, who + "no live aux variable has the lever-arm handle");
+    if (it->second.v->kind != V_AUX || it->second.v->size != 3)
+      throw HpError(UVIO_HP_E_ARG, who + "the lever-arm handle is not a 3-vector");
+  }
+  if (fix_queued_ >= kFixQueueMax)
+    throw HpError(UVIO_HP_E_CAPACITY, who + "more than " + std::to_string(kFixQueueMax) + " fixes queued");
+  m.pose_r = r;
+  m.rot = rot_handle > 0 ? rot_handle : 0;
+  m.aux = arm_handle > 0 ? arm_handle : 0;
   m.thr = chi2_mult * chi2_table_[r];
   past_fix_[t].push_back(m);
   fix_queued_++;
@@ -425,6 +498,7 @@ int Engine::after_tracking(double t, const std::vector<int> &camids, clk::time_p
   timing_ = uvio_hp_timing_t{};
   frame_feats_.clear();
   fix_results_.clear();
+  pose_results_.clear();
   timing_.tracking = secs(rT1, rT2) - early_prop_s_;
   timing_.device_syncs = track_syncs;
   timing_.sync_wait = track_wait;
@@ -505,12 +579,20 @@ int Engine::after_tracking(double t, const std::vector<int> &camids, clk::time_p
         run = propagate_uwb(tf) == 0;
         if (run) reached = tf;
       }
+      const std::vector<FixMeas> &fx = it->second;
       if (!run) {
-        for (size_t k = 0; k < it->second.size(); k++) fix_results_.push_back(FixResult{tf, 0.0, 2});
+        for (const FixMeas &m : fx) (m.pose_r ? pose_results_ : fix_results_).push_back(FixResult{tf, 0.0, 2});
         continue;
       }
       HPROF("fix.chain");
-      fix_update_chain(tf, it->second);
+      // feed order; each run of one kind is its own device chain (a change of kind ends a chain)
+      for (size_t a = 0, b; a < fx.size(); a = b) {
+        for (b = a + 1; b < fx.size() && (fx[b].pose_r != 0) == (fx[a].pose_r != 0); b++) {}
+        if (fx[a].pose_r)
+          pose_update_chain(tf, fx.data() + a, b - a);
+        else
+          fix_update_chain(tf, fx.data() + a, b - a);
+      }
     }
     past_uwb_.erase(past_uwb_.begin(), past_uwb_.upper_bound(t));
     for (auto it = past_fix_.begin(); it != fe; it++) fix_queued_ -= (int)it->second.size();
@@ -1397,15 +1479,16 @@ int Engine::uwb_update_message(const std::vector<std::pair<size_t, double>> &ran
 // [accepted, negative diagonals, chi2, refused | dx]; the host then applies the accepted dx's to its mean in order.
 // An aux lever arm is looked up here, at replay: its covariance offset moves when clones in front of it are
 // marginalized, and a handle removed since the feed refuses its fix (status 3) without touching the state.
-void Engine::fix_update_chain(double t, const std::vector<FixMeas> &fixes) {
+void Engine::fix_update_chain(double t, const FixMeas *fixes, size_t nfix) {
   stage_ = "position fix chain";
   std::vector<const FixMeas *> live;
   std::vector<size_t> slot;  // live fix -> its entry of fix_results_
-  for (const FixMeas &m : fixes) {
+  for (size_t f = 0; f < nfix; f++) {
+    const FixMeas &m = fixes[f];
     fix_results_.push_back(FixResult{t, 0.0, 3});
     if (m.aux > 0) {
       auto it = aux_.find(m.aux);
-      if (it == aux_.end() || it->second.v->size != 3) continue;
+      if (it == aux_.end() || it->second.v->kind != V_AUX || it->second.v->size != 3) continue;
     }
     live.push_back(&m);
     slot.push_back(fix_results_.size() - 1);
@@ -1446,6 +1529,80 @@ void Engine::fix_update_chain(double t, const std::vector<FixMeas> &fixes) {
         continue;
       }
       if (g.neg > 0) throw HpError(UVIO_HP_E_NUMERIC, "position fix EKFUpdate: negative covariance diagonal");
+      apply_dx(reg + kChainHeader);
+      res.status = 0;
+      applied = true;
+    }
+    if (applied) {  // as after an applied uvio_hp_measurement_update
+      odom_invalidate();
+      odom_flush();
+    }
+  }
+}
+
+// The pose fixes of one timestamp as device chains, fix_update_chain's shape with k_pose_rows as the row kernel: the
+// linearization state (IMU pose, every fix's lever arm and mounting rotation) goes up once per chain, each step is
+// three launches (orientation only: the R = 3 instances, full: the R = 6 ones), one readback per chain, apply_dx per
+// accepted step in order (an aux mounting rotation moves by boxplus there as on the device).  Both handles are looked
+// up here, at replay; a dead or retyped one refuses its fix (status 3) without touching the state.
+void Engine::pose_update_chain(double t, const FixMeas *fixes, size_t nfix) {
+  stage_ = "pose fix chain";
+  std::vector<const FixMeas *> live;
+  std::vector<size_t> slot;  // live fix -> its entry of pose_results_
+  for (size_t f = 0; f < nfix; f++) {
+    const FixMeas &m = fixes[f];
+    pose_results_.push_back(FixResult{t, 0.0, 3});
+    if (m.aux > 0) {
+      auto it = aux_.find(m.aux);
+      if (it == aux_.end() || it->second.v->kind != V_AUX || it->second.v->size != 3) continue;
+    }
+    if (m.rot > 0) {
+      auto it = aux_.find(m.rot);
+      if (it == aux_.end() || it->second.v->kind != V_AUX_QUAT) continue;
+    }
+    live.push_back(&m);
+    slot.push_back(pose_results_.size() - 1);
+  }
+  for (size_t c0 = 0; c0 < live.size(); c0 += kFixMaxChain) {
+    const int nf = (int)std::min(live.size() - c0, (size_t)kFixMaxChain);
+    DPoseState st{};
+    std::memcpy(st.q, imu_->val, sizeof(double) * 4);
+    std::memcpy(st.p, imu_->val + 4, sizeof(double) * 3);
+    st.id_imu = imu_->id;
+    st.nf = nf;
+    for (int j = 0; j < nf; j++) {
+      const FixMeas &m = *live[c0 + j];
+      const Var *av = m.aux > 0 ? aux_.at(m.aux).v.get() : nullptr;
+      const Var *rv = m.rot > 0 ? aux_.at(m.rot).v.get() : nullptr;
+      std::memcpy(st.s[j], av ? av->val : m.s, sizeof(double) * 3);
+      std::memcpy(st.qS[j], rv ? rv->val : m.qS, sizeof(double) * 4);
+      std::memcpy(st.zq[j], m.zq, sizeof(m.zq));
+      std::memcpy(st.zp[j], m.z, sizeof(m.z));
+      std::memcpy(st.R[j], m.Rp, sizeof(m.Rp));
+      st.thr[j] = m.thr;
+      st.r[j] = m.pose_r;
+      // an orientation-only fix has no lever-arm columns
+      st.id_arm[j] = (av && m.pose_r == 6) ? av->id : -1;
+      st.id_rot[j] = rv ? rv->id : -1;
+    }
+    DPoseState *dst = stage(&st, 1);
+    stage_flush();
+    const double *host = run_mchain(nf, [&](int j, const DChainRegion *prev, DChainRow *row, DChainRegion *reg) {
+      launch_pose_rows(d_.stream, dst, j, prev, row, reg);
+      launch_chain_M(d_.stream, d_.P, d_.ldp, N_, row, st.r[j], d_.ekf.M);
+      launch_chain_update(d_.stream, d_.P, d_.ldp, N_, d_.ekf.M, row, st.r[j], false, reg);
+    });
+    bool applied = false;
+    for (int j = 0; j < nf; j++) {
+      const double *reg = host + (size_t)j * d_.mchain_stride;
+      const DChainRegion g = chain_header(reg);
+      FixResult &res = pose_results_[slot[c0 + j]];
+      res.chi2 = g.chi2;
+      if (g.accepted == 0.0) {
+        res.status = g.extra != 0.0 ? 3 : 1;
+        continue;
+      }
+      if (g.neg > 0) throw HpError(UVIO_HP_E_NUMERIC, "pose fix EKFUpdate: negative covariance diagonal");
       apply_dx(reg + kChainHeader);
       res.status = 0;
       applied = true;

@@ -211,9 +211,10 @@ constexpr int kMaxEkfRows = 255;        // rows of one direct (uncompressed) EKF
 constexpr int kMaxDynLds = 152 * 1024;  // dynamic LDS budget of the single-workgroup solvers
 // S holds 5 r^2 doubles for r rows
 // Device chains of small measurements (UWB ranges: Engine::uwb_update_message; position fixes:
-// Engine::fix_update_chain): per step three launches, a row kernel (k_uwb_row / k_fix_rows) that moves the chain's
+// Engine::fix_update_chain; pose fixes: Engine::pose_update_chain): per step three launches, a row kernel
+// (k_uwb_row / k_fix_rows / k_pose_rows) that moves the chain's
 // linearization state by the previous step's dx when that was accepted and leaves one DChainRow, then k_chain_M and
-// k_chain_update, which are the same for both.  Step j owns one region of the chain's buffer: this header, then dx
+// k_chain_update, which are the same for all.  Step j owns one region of the chain's buffer: this header, then dx
 // (N doubles).  The host reads every region back in one copy.
 struct DChainRegion {
   double accepted;  // 1.0: P and dx were updated
@@ -240,11 +241,13 @@ inline DChainRegion chain_header(const double *region) {
   return g;
 }
 // what a row kernel leaves for k_chain_M and k_chain_update: r rows over n columns
-constexpr int kChainMaxCols = 14;  // a UWB row: 6 IMU columns, 3 for p_IinU, 5 for the anchor; a fix: 6 or 9
+// columns: a UWB row has 6 for the IMU, 3 for p_IinU, 5 for the anchor; a position fix 6 or 9; a pose fix 6 .. 12
+constexpr int kChainMaxCols = 14;
+constexpr int kChainMaxRows = 6;   // a range: 1; a position fix: 1 .. 3; a pose fix: 3 or 6
 struct DChainRow {
-  double H[3][kChainMaxCols];  // r x n
-  double res[3];
-  double R[9];                 // leading dimension 3 (a range: R[0] = sigma^2)
+  double H[kChainMaxRows][kChainMaxCols];  // r x n
+  double res[kChainMaxRows];
+  double R[kChainMaxRows * kChainMaxRows];  // leading dimension kChainMaxRows (a range: R[0] = sigma^2)
   double thr;                  // chi2 threshold
   int hidx[kChainMaxCols];     // covariance index of H's column k
   int n, pad;
@@ -254,7 +257,8 @@ void launch_chain_M(hipStream_t s, const double *P, int ldp, int N, const DChain
 // S = H M[hidx, :] + R and the step's gate, the same arithmetic in every workgroup; accepted: P -= W W^T and dx.
 //   range (r = 1): chi2 = res^2 / S against row->thr (a NaN chi2 passes, as in UpdaterUWB.cpp:73-79), W = M / sqrt S,
 //                  dx = W res / sqrt S, extra = S
-//   fix (r = 1 .. 3): S = L L^T in registers (a pivot that is not finite or not positive, or a NaN chi2: refused),
+//   fix (r = 1 .. 3; a pose fix: 3 or 6): S = L L^T in registers (a pivot that is not finite or not positive, or a
+//                  NaN chi2: refused),
 //                  chi2 = |L^-1 res|^2 against row->thr, W = M L^-T, dx = W L^-1 res, extra = refused
 void launch_chain_update(hipStream_t s, double *P, int ldp, int N, const double *M, const DChainRow *row, int r,
                          bool range, DChainRegion *region);
@@ -301,6 +305,30 @@ struct DFixState {
 // prev halts this fix too
 void launch_fix_rows(hipStream_t s, DFixState *st, int j, const DChainRegion *prev, DChainRow *row,
                      DChainRegion *region);
+
+// Buffered pose fixes (include/uvio_hp.h uvio_hp_feed_pose; Engine::pose_update_chain): a sensor frame S mounted on the
+// body with rotation q_ItoS and lever arm s = p_SinI, its pose z_q = q_GtoS, z_p = p_SinG reported in G.  Orientation
+// rows first: r_theta = 2 vec(z_q (x) inv(q_ItoS (x) q_GtoI)), H over [dtheta, dp, ds, dphi] = [R_ItoS | 0 | 0 | I];
+// FULL mode adds r_p = z_p - (p_IinG + R_GtoI^T s), H = [-R_GtoI^T [s]x | I | R_GtoI^T | 0].  The ds block exists only
+// with an aux lever arm, the dphi block only with an aux mounting rotation (JPL left error for both quaternions).
+struct DPoseState {
+  double q[4], p[3];               // IMU q_GtoI, p_IinG: the chain's linearization state
+  double qS[kFixMaxChain][4];      // fix j's q_ItoS (an aux one moves by boxplus with every accepted dx)
+  double s[kFixMaxChain][3];       // fix j's lever arm (an aux one moves additively)
+  double zq[kFixMaxChain][4];
+  double zp[kFixMaxChain][3];
+  double R[kFixMaxChain][36];      // r x r at leading dimension kChainMaxRows, symmetric
+  double thr[kFixMaxChain];        // chi2 threshold (INFINITY: no gate)
+  int r[kFixMaxChain];             // 3: orientation only; 6: orientation, then position
+  int id_arm[kFixMaxChain];        // covariance id of the aux lever arm, < 0: constant
+  int id_rot[kFixMaxChain];        // covariance id of the aux mounting rotation, < 0: constant
+  int id_imu, nf;
+};
+// fix j: move the linearization state by fix j-1's dx if that was accepted (IMU q and aux rotations by boxplus, p and
+// aux arms additively), form the row block over the columns [IMU (6), arm (3) if aux, rotation (3) if aux] and reset
+// the region's header; a negative diagonal or a halt in prev halts this fix too
+void launch_pose_rows(hipStream_t s, DPoseState *st, int j, const DChainRegion *prev, DChainRow *row,
+                      DChainRegion *region);
 constexpr int kChainMaxSteps = kUwbMaxRanges > kFixMaxChain ? kUwbMaxRanges : kFixMaxChain;
 
 struct EkfScratch {

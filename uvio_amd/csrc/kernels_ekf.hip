@@ -18,8 +18,8 @@
 // products) cost 96 us per update at cfg2 in rocprof (profiles/r01g_cfg2_per_frame.txt).
 //
 // Also here: the delayed-initialization candidate (k_di_M, k_di_S, k_chain_apply) and the device chains of small
-// measurements, UWB ranges and position fixes: a row kernel (k_uwb_row / k_fix_rows), then k_chain_M and
-// k_chain_update<RangeGate | FixGate<R>> for both.
+// measurements, UWB ranges, position fixes and pose fixes: a row kernel (k_uwb_row / k_fix_rows / k_pose_rows), then
+// k_chain_M and k_chain_update<RangeGate | FixGate<R>> for all three.
 //
 // MFMA operand layout (f64 16x16x4): A (16x4) lane l holds A[l & 15][l >> 4]; B (4x16) lane l holds
 // B[l >> 4][l & 15]; C/D register q of lane l is D[(l >> 4) + 4 q][l & 15].
@@ -446,7 +446,7 @@ __global__ void k_fix_rows(DFixState *st, int j, const DChainRegion *__restrict_
     o.res[a] = u.z[j][a] - dot3(c, pred);
   }
   for (int k = 0; k < 9; k++) {
-    o.R[k] = u.R[j][k];
+    o.R[kChainMaxRows * (k / 3) + k % 3] = u.R[j][k];
     o.hidx[k] = k < 6 ? u.id_imu + k : (aux ? u.id_aux[j] + k - 6 : 0);
   }
   o.thr = u.thr[j];
@@ -458,6 +458,74 @@ __global__ void k_fix_rows(DFixState *st, int j, const DChainRegion *__restrict_
 void launch_fix_rows(hipStream_t s, DFixState *st, int j, const DChainRegion *prev, DChainRow *row,
                      DChainRegion *region) {
   hipLaunchKernelGGL(k_fix_rows, dim3(1), dim3(64), 0, s, st, j, prev, row, region);
+}
+
+// Chained pose fixes (kernels.h DPoseState)
+__global__ void k_pose_rows(DPoseState *st, int j, const DChainRegion *__restrict__ prev, DChainRow *__restrict__ row,
+                            DChainRegion *__restrict__ region) {
+  if (threadIdx.x != 0) return;
+  DPoseState &u = *st;
+  bool halt;
+  if (const double *dx = chain_prev_dx(prev, halt)) {
+    // Var::update of the previous fix's dx: IMU quaternion boxplus + position, the aux lever arms additive, the aux
+    // mounting rotations by boxplus.  Two fixes that name one variable carry equal copies, which move alike.
+    quat_boxplus(u.q, dx + u.id_imu);
+    for (int k = 0; k < 3; k++) u.p[k] += dx[u.id_imu + 3 + k];
+    for (int a = 0; a < u.nf; a++) {
+      if (u.id_arm[a] >= 0)
+        for (int k = 0; k < 3; k++) u.s[a][k] += dx[u.id_arm[a] + k];
+      if (u.id_rot[a] >= 0) quat_boxplus(u.qS[a], dx + u.id_rot[a]);
+    }
+  }
+  const int r = u.r[j];
+  const bool arm = u.id_arm[j] >= 0, rot = u.id_rot[j] >= 0;
+  const int c_arm = 6, c_rot = arm ? 9 : 6, n = c_rot + (rot ? 3 : 0);
+  const double *s = u.s[j];
+  double Rm[9], RS[9], qp[4], qi[4], dq[4];
+  quat_2_Rot(u.q, Rm);      // R_GtoI
+  quat_2_Rot(u.qS[j], RS);  // R_ItoS
+  quat_multiply(u.qS[j], u.q, qp);  // q_GtoS
+  qi[0] = -qp[0], qi[1] = -qp[1], qi[2] = -qp[2], qi[3] = qp[3];
+  quat_multiply(u.zq[j], qi, dq);  // w >= 0 (quat_multiply)
+  DChainRow &o = *row;
+  for (int a = 0; a < kChainMaxRows; a++) {
+    for (int k = 0; k < kChainMaxCols; k++) o.H[a][k] = 0.0;
+    o.res[a] = 0.0;
+  }
+  for (int a = 0; a < 3; a++) {
+    for (int k = 0; k < 3; k++) o.H[a][k] = RS[3 * a + k];
+    if (rot) o.H[a][c_rot + a] = 1.0;
+    o.res[a] = 2.0 * dq[a];
+  }
+  if (r == 6) {
+    double Sx[9], A[9], pred[3];
+    m3t_vec(Rm, s, pred);  // R_GtoI^T s
+    skew(s, Sx);
+    m3_mul_at(Rm, Sx, A);  // R_GtoI^T [s]x
+    for (int a = 0; a < 3; a++) {
+      for (int k = 0; k < 3; k++) {
+        o.H[3 + a][k] = -A[3 * a + k];
+        if (arm) o.H[3 + a][c_arm + k] = Rm[3 * k + a];
+      }
+      o.H[3 + a][3 + a] = 1.0;
+      o.res[3 + a] = u.zp[j][a] - (u.p[a] + pred[a]);
+    }
+  }
+  for (int k = 0; k < kChainMaxRows * kChainMaxRows; k++) o.R[k] = u.R[j][k];
+  for (int k = 0; k < kChainMaxCols; k++)
+    o.hidx[k] = k < 6              ? u.id_imu + k
+                : (arm && k < 9) ? u.id_arm[j] + k - c_arm
+                : (rot && k < n) ? u.id_rot[j] + k - c_rot
+                                 : 0;
+  o.thr = u.thr[j];
+  o.n = n;
+  o.pad = 0;
+  chain_reset(region, halt);
+}
+
+void launch_pose_rows(hipStream_t s, DPoseState *st, int j, const DChainRegion *prev, DChainRow *row,
+                      DChainRegion *region) {
+  hipLaunchKernelGGL(k_pose_rows, dim3(1), dim3(64), 0, s, st, j, prev, row, region);
 }
 
 template <int R>
@@ -480,8 +548,8 @@ __global__ void __launch_bounds__(256) k_chain_M(const double *__restrict__ P, i
 }
 
 void launch_chain_M(hipStream_t s, const double *P, int ldp, int N, const DChainRow *row, int r, double *M) {
-  if (r < 1 || r > 3) throw std::runtime_error("measurement chain: " + std::to_string(r) + " rows");
-  auto *k = r == 1 ? k_chain_M<1> : r == 2 ? k_chain_M<2> : k_chain_M<3>;
+  if (r != 1 && r != 2 && r != 3 && r != 6) throw std::runtime_error("measurement chain: " + std::to_string(r) + " rows");
+  auto *k = r == 1 ? k_chain_M<1> : r == 2 ? k_chain_M<2> : r == 3 ? k_chain_M<3> : k_chain_M<kChainMaxRows>;
   hipLaunchKernelGGL(k, dim3((N + 255) / 256), dim3(256), 0, s, P, ldp, N, row, M);
 }
 
@@ -580,7 +648,7 @@ __global__ void __launch_bounds__(256) k_chain_update(double *__restrict__ P, in
     for (int b = a; b < R; b++) {
       double acc = 0.0;
       for (int k = 0; k < n; k++) acc = fma(row->H[a][k], M[(size_t)b * N + row->hidx[k]], acc);
-      S[a][b] = acc + row->R[3 * a + b];
+      S[a][b] = acc + row->R[kChainMaxRows * a + b];
     }
   G g;
   double chi2, extra;
@@ -610,13 +678,14 @@ __global__ void __launch_bounds__(256) k_chain_update(double *__restrict__ P, in
 
 void launch_chain_update(hipStream_t s, double *P, int ldp, int N, const double *M, const DChainRow *row, int r,
                          bool range, DChainRegion *region) {
-  if (r < 1 || r > 3 || (range && r != 1))
+  if ((r != 1 && r != 2 && r != 3 && r != 6) || (range && r != 1))
     throw std::runtime_error("measurement chain: " + std::to_string(r) + " rows");
   const int nb = (N + 15) / 16;
   auto *k = range    ? k_chain_update<RangeGate>
             : r == 1 ? k_chain_update<FixGate<1>>
             : r == 2 ? k_chain_update<FixGate<2>>
-                     : k_chain_update<FixGate<3>>;
+            : r == 3 ? k_chain_update<FixGate<3>>
+                     : k_chain_update<FixGate<kChainMaxRows>>;
   hipLaunchKernelGGL(k, dim3(nb * (nb + 1) / 2), dim3(256), 0, s, P, ldp, N, M, row, region, nb);
 }
 

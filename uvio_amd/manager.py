@@ -407,13 +407,27 @@ class VioManager:
                                C.byref(h)), "aux_add_from_measurement")
         return h.value
 
+    def add_quat_state(self, q, prior_cov, walk_sigma=None):
+        """A new JPL unit quaternion [x y z w] of the caller's own (a mounting rotation): 3 error dimensions, updated
+        as q <- dq(dtheta) (x) q.  prior_cov (3, 3) over dtheta (upper triangle read); walk_sigma in rad / sqrt(s)
+        (None: a constant).  q is normalized on entry.  Returns the handle; aux_state gives 4 values for it."""
+        q = np.ascontiguousarray(q, dtype=np.float64).reshape(4)
+        pr = np.ascontiguousarray(np.asarray(prior_cov, dtype=np.float64).reshape(3, 3))
+        w, wp = self._walk(walk_sigma, 3)
+        h = C.c_int(0)
+        self._check(self._call("aux_add_quat", self._h, _dp(q), _dp(pr), 3, wp, C.byref(h)), "aux_add_quat")
+        return h.value
+
     def aux_state(self, handle):
         """(covariance offset, value) of an aux variable now.  The offset moves when clones or landmarks in front
-        of the variable are marginalized: ask before building an H."""
+        of the variable are marginalized: ask before building an H.  A quaternion variable (add_quat_state) has 3
+        error columns at the offset and a value of 4."""
         vid, dim = C.c_int(), C.c_int()
-        val = np.zeros(N.AUX_MAX_DIM)
+        val = np.full(N.AUX_MAX_DIM, np.nan)
         self._check(self._call("aux_get", self._h, int(handle), C.byref(vid), C.byref(dim), _dp(val)), "aux_get")
-        return vid.value, val[:dim.value].copy()
+        # a quaternion variable reports dim = 3 and writes 4 doubles (values are always finite)
+        k = 4 if dim.value == 3 and np.isfinite(val[3]) else dim.value
+        return vid.value, val[:k].copy()
 
     def remove_state(self, handle):
         """Marginalize an aux variable; the handle is dead afterwards."""
@@ -456,6 +470,46 @@ class VioManager:
                                None if s is None else _dp(s), int(aux_handle), C.c_double(chi2_mult),
                                C.byref(queued)), "feed_measurement_position")
         return bool(queued.value)
+
+    # ---- buffered pose fixes (uvio_hp_feed_pose) ----
+    def feed_measurement_pose(self, t, z_q, R, z_p=None, q_ItoS=None, rot_handle=0, p_SinI=None, arm_handle=0,
+                              chi2_mult=1.0):
+        """Queue the pose fix of a sensor frame S at time t: z_q = q_GtoS (JPL [x y z w]) and, with z_p = p_SinG given,
+        the position too (R (6, 6), orientation rows first; without z_p R is (3, 3)).  The mounting rotation is the
+        constant q_ItoS (None: identity) or, with rot_handle > 0, a variable of add_quat_state; the lever arm the
+        constant p_SinI (None: zero) or, with arm_handle > 0, a 3-dimensional variable of add_state.  Gated at
+        chi2_mult * chi2_95(r) (inf: no gate).  Replayed inside the next camera or simulation feed in time order with
+        the UWB messages and the position fixes.  Returns True when queued."""
+        full = z_p is not None
+        r = 6 if full else 3
+        z_q = np.ascontiguousarray(z_q, dtype=np.float64).reshape(4)
+        R = np.ascontiguousarray(np.asarray(R, dtype=np.float64).reshape(r, r))
+        zp = np.ascontiguousarray(z_p, dtype=np.float64).reshape(3) if full else None
+        qs = None
+        if int(rot_handle) <= 0:
+            qs = np.ascontiguousarray([0.0, 0.0, 0.0, 1.0] if q_ItoS is None else q_ItoS, dtype=np.float64).reshape(4)
+        s = None
+        if int(arm_handle) <= 0:
+            s = np.ascontiguousarray(np.zeros(3) if p_SinI is None else p_SinI, dtype=np.float64).reshape(3)
+        queued = C.c_int(0)
+        self._check(self._call("feed_pose", self._h, C.c_double(t), N.POSE_FULL if full else N.POSE_ORIENTATION,
+                               _dp(z_q), None if zp is None else _dp(zp), _dp(R), r, None if qs is None else _dp(qs),
+                               int(rot_handle), None if s is None else _dp(s), int(arm_handle), C.c_double(chi2_mult),
+                               C.byref(queued)), "feed_measurement_pose")
+        return bool(queued.value)
+
+    def pose_results(self):
+        """The pose fixes the last camera or simulation feed consumed, in processing order: a list of
+        {"t", "chi2", "status"}; status 0 applied, 1 gated, 2 dropped, 3 refused."""
+        n = C.c_int(0)
+        rc = self._call("get_pose_results", self._h, None, None, None, 0, C.byref(n))
+        if rc != N.E_CAPACITY:
+            self._check(rc, "get_pose_results")
+        k = n.value
+        t, chi2, st = np.zeros(max(k, 1)), np.zeros(max(k, 1)), np.zeros(max(k, 1), dtype=np.int32)
+        self._check(self._call("get_pose_results", self._h, _dp(t), _dp(chi2), st.ctypes.data_as(C.POINTER(C.c_int)),
+                               k, C.byref(n)), "get_pose_results")
+        return [{"t": float(t[i]), "chi2": float(chi2[i]), "status": int(st[i])} for i in range(k)]
 
     def position_results(self):
         """The fixes the last camera or simulation feed consumed, in processing order: a list of
@@ -929,6 +983,35 @@ def position_update_p(P, imu_id, q_GtoI, p_IinG, s, Cm, z, R, aux_id=-1, chi2_th
                                              _dp(Cm), _dp(z), _dp(R), R.shape[1], float(chi2_thr), _dp(dx),
                                              C.byref(chi2), C.byref(applied))
     N.check(rc, what="uvio_hp_debug_position_update_p")
+    return buf, dx, chi2.value, bool(applied.value)
+
+
+def pose_update_p(P, imu_id, q_GtoI, p_IinG, s, q_ItoS, z_q, R, z_p=None, arm_id=-1, rot_id=-1, chi2_thr=float("inf"),
+                  ld=None):
+    """uvio_hp_debug_pose_update_p: k_pose_rows -> k_chain_M -> k_chain_update for one pose fix on a standalone
+    covariance.  The IMU pose's error columns start at imu_id, the lever arm s's at arm_id and the mounting rotation
+    q_ItoS's at rot_id (< 0: a constant).  z_p None: orientation only, R (3, r'); else R (6, r'), r' >= r its leading
+    dimension.  Returns (buf, dx, chi2, applied): the (N, ld) buffer as it came back (padding included); not applied: P
+    unchanged, dx zeros."""
+    full = z_p is not None
+    R = np.ascontiguousarray(R, dtype=np.float64)
+    q = np.ascontiguousarray(q_GtoI, dtype=np.float64).reshape(4)
+    p = np.ascontiguousarray(p_IinG, dtype=np.float64).reshape(3)
+    s = np.ascontiguousarray(s, dtype=np.float64).reshape(3)
+    qs = np.ascontiguousarray(q_ItoS, dtype=np.float64).reshape(4)
+    zq = np.ascontiguousarray(z_q, dtype=np.float64).reshape(4)
+    zp = np.ascontiguousarray(z_p, dtype=np.float64).reshape(3) if full else None
+    Nn = np.shape(P)[0]
+    ld = Nn if ld is None else int(ld)
+    buf = _padded(P, Nn, ld)
+    dx = np.zeros(Nn)
+    chi2, applied = C.c_double(0.0), C.c_int(0)
+    lib = N.load()
+    rc = lib.uvio_hp_debug_pose_update_p(_dp(buf), Nn, ld, int(imu_id), _dp(q), _dp(p), int(arm_id), _dp(s), int(rot_id),
+                                         _dp(qs), N.POSE_FULL if full else N.POSE_ORIENTATION, _dp(zq),
+                                         None if zp is None else _dp(zp), _dp(R), R.shape[1], float(chi2_thr), _dp(dx),
+                                         C.byref(chi2), C.byref(applied))
+    N.check(rc, what="uvio_hp_debug_pose_update_p")
     return buf, dx, chi2.value, bool(applied.value)
 
 
