@@ -46,6 +46,15 @@ extern "C" {
 /* uvio_hp_feed_pose's mode: the rows of a pose fix */
 #define UVIO_HP_POSE_ORIENTATION 1 /* 3 rows: orientation only */
 #define UVIO_HP_POSE_FULL 2        /* 6 rows: orientation, then position */
+/* uvio_hp_debug_cov_propagate_p's path selector and the path it reports */
+#define UVIO_HP_COV_PATH_AUTO 0  /* the engine's own rule */
+#define UVIO_HP_COV_PATH_SPLIT 1 /* k_prop_T + k_prop_write (+ k_clone) */
+#define UVIO_HP_COV_PATH_FUSED 2 /* k_prop_clone, or refuse */
+/* uvio_hp_debug_cov_gather_p's kernel */
+#define UVIO_HP_COV_MARGINALIZE 0       /* k_marginalize (m0, ms) */
+#define UVIO_HP_COV_MARGINALIZE_MULTI 1 /* k_marginalize_multi (kept indices, ascending) */
+#define UVIO_HP_COV_COMPACT 2           /* k_compact (kept indices) */
+#define UVIO_HP_COV_MARGINAL_GATHER 3   /* k_marginal_gather (any indices) */
 
 /* ---- option structs: the keys of estimator_config.yaml / kalibr_*.yaml / uwb_*.yaml ---- */
 
@@ -668,6 +677,36 @@ int uvio_hp_debug_pose_update_p(double *P, int N, int ld, int imu_id, const doub
                                 const double *s, int rot_id, const double *q_ItoS, int mode, const double *z_q,
                                 const double *z_p, const double *R, int ldr, double chi2_thr, double *dx, double *chi2,
                                 int *applied);
+/* StateHelper::EKFPropagation (StateHelper.cpp:36-114), optionally followed by the clone of the 6-wide IMU pose with
+ * its time-offset term (StateHelper.cpp:341-391, 579-616), on a caller's host covariance at shapes a test chooses.  P
+ * holds N rows (N + 6 with a clone) of ld doubles, ld >= that row count; the rows go up with their padding, the kernels
+ * run at leading dimension ld, the rows come back (N + 6 wide with a clone).  The new block is rows / columns
+ * s0 .. s0 + p - 1, or the p distinct indices rows[] (rows != NULL: several variables with a block-row Phi; s0 is
+ * not read); iold[q]: the distinct columns Phi (p x q, packed) multiplies; Q (p x p, packed): only its upper triangle
+ * is read.  clone != 0: the pose at src0 .. src0 + 5 is cloned to N .. N + 5; dt_id >= 0 adds the time-offset term
+ * with column dt_id and dnc[6]; dt_id < 0: no such term (dnc may be NULL).
+ * path: UVIO_HP_COV_PATH_AUTO takes what Engine::cov_propagate_clone would take for (N, p, q) -- one k_prop_clone
+ * launch when p <= 32, q <= 32 and N p <= 8192, else k_prop_T, k_prop_write and k_clone; _SPLIT forces the latter;
+ * _FUSED the former.  *path_ran receives _SPLIT or _FUSED (without a clone always _SPLIT).
+ * Before any device work: UVIO_HP_E_ARG for a null pointer, ld below the row count, p or q < 1, an index outside
+ * [0, N), a repeated index in rows or iold, rows together with a clone, an unknown path, _FUSED without a clone;
+ * UVIO_HP_E_CAPACITY for p > 64 or q > 256 (Engine::cov_propagate's limits) and for _FUSED on a shape k_prop_clone
+ * does not take. */
+int uvio_hp_debug_cov_propagate_p(double *P, int N, int ld, int s0, int p, const int *rows, const int *iold, int q,
+                                  const double *Phi, const double *Q, int clone, int src0, int dt_id, const double *dnc,
+                                  int path, int *path_ran);
+/* The kernels that copy the covariance into a smaller one, on a caller's host covariance P (N rows of ld doubles,
+ * ld >= N >= 1, only read).  op selects:
+ *   UVIO_HP_COV_MARGINALIZE        StateHelper::marginalize of [m0, m0 + ms), ms >= 1, m0 + ms <= N; Nn = N - ms
+ *   UVIO_HP_COV_MARGINALIZE_MULTI  several of them in one launch: idx[n] the kept indices, strictly ascending; Nn = n
+ *   UVIO_HP_COV_COMPACT            P[idx, idx]: idx[n] in [0, N), n <= N, any order; Nn = n
+ *   UVIO_HP_COV_MARGINAL_GATHER    uvio_hp_get_marginal_cov's gather: idx[n] in [0, N), any order, repeats allowed,
+ *                                  n <= 4096 (else UVIO_HP_E_CAPACITY)
+ * out: Nn rows of ld doubles for the first three (uploaded first, so whatever the kernel leaves alone comes back as
+ * it was), n x n packed for the gather.  Nn = 0 launches nothing and returns 0.  UVIO_HP_E_ARG before any device
+ * work for a null pointer, ld < N, an unknown op or an index outside its range. */
+int uvio_hp_debug_cov_gather_p(const double *P, int N, int ld, int op, int m0, int ms, const int *idx, int n,
+                               double *out);
 /* boost::math::quantile(chi_squared(dof), 0.95), the table every reference updater multiplies its chi2_multipler
  * into (UpdaterMSCKF.cpp:52-55, UpdaterSLAM.cpp:55-58, UpdaterZeroVelocity.cpp:59-62, UpdaterUWB.h:33-36), for
  * dof 1 .. 999; UVIO_HP_E_ARG outside that range. */

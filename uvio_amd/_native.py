@@ -13,6 +13,8 @@ MAX_CAMS = 4
 MAX_ANCHORS = 16
 AUX_MAX_DIM = 8
 POSE_ORIENTATION, POSE_FULL = 1, 2  # uvio_hp_feed_pose's mode
+COV_PATH_AUTO, COV_PATH_SPLIT, COV_PATH_FUSED = 0, 1, 2  # uvio_hp_debug_cov_propagate_p's path
+COV_MARGINALIZE, COV_MARGINALIZE_MULTI, COV_COMPACT, COV_MARGINAL_GATHER = 0, 1, 2, 3  # uvio_hp_debug_cov_gather_p's op
 
 OK = 0
 E_ARG, E_STATE, E_DEVICE, E_NUMERIC, E_CONFIG, E_ORDER, E_CAPACITY, E_INTERNAL = -1, -2, -3, -4, -5, -6, -7, -8
@@ -199,6 +201,9 @@ SIGNATURES = [
     ("get_position_results", _I, [C.c_void_p, _P(_D), _P(_D), _P(_I), _I, _P(_I)]),
     ("debug_position_update_p", _I, [_P(_D), _I, _I, _I, _P(_D), _P(_D), _I, _P(_D), _I, _P(_D), _P(_D), _P(_D), _I, _D,
                                      _P(_D), _P(_D), _P(_I)]),
+    ("debug_cov_propagate_p", _I, [_P(_D), _I, _I, _I, _I, _P(_I), _P(_I), _I, _P(_D), _P(_D), _I, _I, _I, _P(_D), _I,
+                                   _P(_I)]),
+    ("debug_cov_gather_p", _I, [_P(_D), _I, _I, _I, _I, _I, _P(_I), _I, _P(_D)]),
 ]
 
 # uvio_hp_allreduce_fn: int (*)(double *buf, size_t count, void *user)

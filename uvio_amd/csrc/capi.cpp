@@ -448,6 +448,28 @@ int uvio_hp_aux_walk_p(double *P, int N, int ld, int ntab, const int *ids, const
     return UVIO_HP_E_DEVICE;
   }
 }
+int uvio_hp_debug_cov_propagate_p(double *P, int N, int ld, int s0, int p, const int *rows, const int *iold, int q,
+                                  const double *Phi, const double *Q, int clone, int src0, int dt_id, const double *dnc,
+                                  int path, int *path_ran) {
+  try {
+    return Engine::cov_propagate_standalone(P, N, ld, s0, p, rows, iold, q, Phi, Q, clone, src0, dt_id, dnc, path,
+                                            path_ran);
+  } catch (const HpError &ex) {
+    return ex.code;
+  } catch (...) {
+    return UVIO_HP_E_DEVICE;
+  }
+}
+int uvio_hp_debug_cov_gather_p(const double *P, int N, int ld, int op, int m0, int ms, const int *idx, int n,
+                               double *out) {
+  try {
+    return Engine::cov_gather_standalone(P, N, ld, op, m0, ms, idx, n, out);
+  } catch (const HpError &ex) {
+    return ex.code;
+  } catch (...) {
+    return UVIO_HP_E_DEVICE;
+  }
+}
 
 // ---- buffered position fixes (engine_update.cpp) ----
 int uvio_hp_feed_position(uvio_hp_t *h, double t, int r, const double *C, const double *z, const double *R, int ldr,

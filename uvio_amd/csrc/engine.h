@@ -544,6 +544,12 @@ class Engine {
                                  int ldhx, const double *H_auxinv, const double *R, int ldr);
   static int aux_walk_standalone(double *P, int N, int ld, int ntab, const int *ids, const int *dims,
                                  const double *sigma2, double dt);
+  // the covariance bookkeeping kernels on a caller's host covariance (uvio_hp_debug_cov_propagate_p / _cov_gather_p)
+  static int cov_propagate_standalone(double *P, int N, int ld, int s0, int p, const int *rows, const int *iold, int q,
+                                      const double *Phi, const double *Q, int clone, int src0, int dt_id,
+                                      const double *dnc, int path, int *path_ran);
+  static int cov_gather_standalone(const double *P, int N, int ld, int op, int m0, int ms, const int *idx, int n,
+                                   double *out);
   // the three kernels of the position-fix chain on a caller's host covariance (uvio_hp_debug_position_update_p)
   static int position_update_standalone(double *P, int N, int ld, int imu_id, const double *q, const double *p,
                                         int aux_id, const double *s, int r, const double *C, const double *z,

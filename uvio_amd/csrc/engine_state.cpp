@@ -460,8 +460,7 @@ void Engine::check_neg_diag(const char *who) {
 bool Engine::cov_propagate_clone(int s0, int p, const std::vector<int> &iold, const std::vector<double> &Phi,
                                  const std::vector<double> &Q, bool do_dt, const double *ddnc) {
   const int q = (int)iold.size();
-  if (p > 32 || q > 32 || N_ + 6 > d_.ldp || N_ * p > 8 * 1024)
-    return false;  // (launch_prop_clone's bounds)
+  if (!prop_clone_fits(N_, p, q) || N_ + 6 > d_.ldp) return false;
   const double *dPhi = stage(Phi.data(), (size_t)p * q);
   const double *dQ = stage(Q.data(), (size_t)p * p);
   const int *diold = stage(iold.data(), (size_t)q);
@@ -1105,6 +1104,110 @@ int Engine::aux_walk_standalone(double *P, int N, int ld, int ntab, const int *i
     HP_HIP(hipMemcpyAsync(dI, cidx.data(), sizeof(int) * m, hipMemcpyHostToDevice, s));
     launch_aux_walk(s, dP, ld, dI, ds2, m, dt);
   });
+}
+
+// n indices, each in [0, N); distinct when asked
+static bool cov_indices_ok(const int *v, int n, int N, bool distinct) {
+  std::vector<uint8_t> seen((size_t)std::max(N, 0), 0);
+  for (int k = 0; k < n; k++) {
+    if (v[k] < 0 || v[k] >= N) return false;
+    if (distinct && seen[(size_t)v[k]]++) return false;
+  }
+  return true;
+}
+
+// Engine::cov_propagate / cov_propagate_clone + clone_imu_pose's launches on a caller's covariance
+int Engine::cov_propagate_standalone(double *P, int N, int ld, int s0, int p, const int *rows, const int *iold, int q,
+                                     const double *Phi, const double *Q, int clone, int src0, int dt_id,
+                                     const double *dnc, int path, int *path_ran) {
+  if (!P || !iold || !Phi || !Q || !path_ran) return UVIO_HP_E_ARG;
+  const bool do_clone = clone != 0, do_dt = do_clone && dt_id >= 0;
+  if (N < 1 || p < 1 || q < 1 || (long long)N + (do_clone ? 6 : 0) > ld) return UVIO_HP_E_ARG;
+  if (path != UVIO_HP_COV_PATH_AUTO && path != UVIO_HP_COV_PATH_SPLIT && path != UVIO_HP_COV_PATH_FUSED)
+    return UVIO_HP_E_ARG;
+  if ((rows && do_clone) || (path == UVIO_HP_COV_PATH_FUSED && !do_clone) || (do_dt && !dnc)) return UVIO_HP_E_ARG;
+  if (p > 64 || q > 256) return UVIO_HP_E_CAPACITY;  // (Engine::cov_propagate's limits)
+  if (rows ? !cov_indices_ok(rows, p, N, true) : (s0 < 0 || (long long)s0 + p > N)) return UVIO_HP_E_ARG;
+  if (!cov_indices_ok(iold, q, N, true)) return UVIO_HP_E_ARG;
+  if (do_clone && (src0 < 0 || (long long)src0 + 6 > N || dt_id >= N)) return UVIO_HP_E_ARG;
+  const bool fits = do_clone && prop_clone_fits(N, p, q);
+  if (path == UVIO_HP_COV_PATH_FUSED && !fits) return UVIO_HP_E_CAPACITY;
+  const bool fused = fits && path != UVIO_HP_COV_PATH_SPLIT;
+  // [Phi | Q | dnc] as one table
+  const size_t nPhi = (size_t)p * q, nQ = (size_t)p * p;
+  std::vector<double> tab(nPhi + nQ + 6, 0.0);
+  std::copy(Phi, Phi + nPhi, tab.begin());
+  std::copy(Q, Q + nQ, tab.begin() + (ptrdiff_t)nPhi);
+  if (do_dt) std::copy(dnc, dnc + 6, tab.begin() + (ptrdiff_t)(nPhi + nQ));
+  std::vector<int> itab(iold, iold + q);
+  if (rows) itab.insert(itab.end(), rows, rows + p);
+  DevBuf<double> dtab, dT;
+  DevBuf<int> dI;
+  const int rc = aux_standalone_run(P, (size_t)N + (do_clone ? 6 : 0), ld, [&](hipStream_t s, double *dP) {
+    dtab = DevBuf<double>(tab.size());
+    dT = DevBuf<double>((size_t)N * p);
+    dI = DevBuf<int>(itab.size());
+    HP_HIP(hipMemcpyAsync(dtab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, s));
+    HP_HIP(hipMemcpyAsync(dI, itab.data(), sizeof(int) * itab.size(), hipMemcpyHostToDevice, s));
+    const double *dPhi = dtab, *dQ = dtab + nPhi, *ddnc = dtab + nPhi + nQ;
+    const int did = do_dt ? dt_id : 0;
+    if (fused) {
+      if (!launch_prop_clone(s, dP, ld, N, s0, p, dI, q, dPhi, dQ, dT, src0, did, ddnc, do_dt ? 1 : 0))
+        throw HpError(UVIO_HP_E_CAPACITY, "fused propagation refused after the size check");
+      return;
+    }
+    launch_cov_propagate(s, dP, ld, N, s0, p, dI, q, dPhi, dQ, dT, rows ? dI + q : nullptr);
+    if (do_clone) launch_clone(s, dP, ld, N, src0, did, ddnc, do_dt ? 1 : 0);
+  });
+  if (rc) return rc;
+  *path_ran = fused ? UVIO_HP_COV_PATH_FUSED : UVIO_HP_COV_PATH_SPLIT;
+  return 0;
+}
+
+// Engine::marginalize / marginalize_many / marginalize_slots / the marginal-covariance gather's launch on a caller's
+// covariance, into a caller's output
+int Engine::cov_gather_standalone(const double *P, int N, int ld, int op, int m0, int ms, const int *idx, int n,
+                                  double *out) {
+  if (!P || !out || N < 1 || ld < N) return UVIO_HP_E_ARG;
+  int Nn = 0;
+  if (op == UVIO_HP_COV_MARGINALIZE) {
+    if (m0 < 0 || ms < 1 || (long long)m0 + ms > N) return UVIO_HP_E_ARG;
+    Nn = N - ms;
+  } else if (op == UVIO_HP_COV_MARGINALIZE_MULTI || op == UVIO_HP_COV_COMPACT || op == UVIO_HP_COV_MARGINAL_GATHER) {
+    if (n < 0 || (n > 0 && !idx)) return UVIO_HP_E_ARG;
+    if (op == UVIO_HP_COV_MARGINAL_GATHER ? n > 4096 : n > N)
+      return op == UVIO_HP_COV_MARGINAL_GATHER ? UVIO_HP_E_CAPACITY : UVIO_HP_E_ARG;
+    if (!cov_indices_ok(idx, n, N, false)) return UVIO_HP_E_ARG;
+    if (op == UVIO_HP_COV_MARGINALIZE_MULTI)
+      for (int k = 1; k < n; k++)
+        if (idx[k] <= idx[k - 1]) return UVIO_HP_E_ARG;  // (the kept indices, in the covariance's order)
+    Nn = n;
+  } else {
+    return UVIO_HP_E_ARG;
+  }
+  if (Nn == 0) return 0;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return UVIO_HP_E_DEVICE;
+  const bool dense = op == UVIO_HP_COV_MARGINAL_GATHER;
+  const size_t nout = (size_t)Nn * (dense ? (size_t)Nn : (size_t)ld);
+  Stream s = Stream::create();
+  DevBuf<double> dP((size_t)N * ld), dout(nout);
+  DevBuf<int> dI((size_t)std::max(n, 1));
+  HP_HIP(hipMemcpyAsync(dP, P, sizeof(double) * (size_t)N * ld, hipMemcpyHostToDevice, s));
+  HP_HIP(hipMemcpyAsync(dout, out, sizeof(double) * nout, hipMemcpyHostToDevice, s));
+  if (op != UVIO_HP_COV_MARGINALIZE) HP_HIP(hipMemcpyAsync(dI, idx, sizeof(int) * n, hipMemcpyHostToDevice, s));
+  if (op == UVIO_HP_COV_MARGINALIZE)
+    launch_marginalize(s, dP, dout, ld, N, m0, ms);
+  else if (op == UVIO_HP_COV_MARGINALIZE_MULTI)
+    launch_marginalize_multi(s, dP, dout, ld, Nn, dI);
+  else if (op == UVIO_HP_COV_COMPACT)
+    launch_compact(s, dP, dout, ld, Nn, dI);
+  else
+    launch_marginal_gather(s, dP, ld, dI, Nn, dout);
+  HP_HIP(hipGetLastError());
+  HP_HIP(hipMemcpyAsync(out, dout, sizeof(double) * nout, hipMemcpyDeviceToHost, s));
+  HP_HIP(hipStreamSynchronize(s));  // nothing in flight when the buffers go
+  return 0;
 }
 
 // One position fix through k_fix_rows -> k_chain_M -> k_chain_update (Engine::fix_update_chain's launches for a chain

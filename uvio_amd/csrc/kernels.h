@@ -139,7 +139,15 @@ void launch_cov_propagate(hipStream_t s, double *P, int ld, int N, int s0, int p
                           const double *Phi, const double *Q, double *T, const int *rows = nullptr);
 // StateHelper::clone of imu->pose() + augment_clone time-offset term (StateHelper.cpp:341-391,579-616)
 void launch_clone(hipStream_t s, double *P, int ld, int N, int src0, int dt_id, const double *dnc_dev, int do_dt);
-// launch_cov_propagate (contiguous block) + launch_clone in one launch; false (nothing launched) when too large
+// The one dispatch rule of the fused propagation + clone (k_prop_clone): a single workgroup of kPropCloneThreads
+// threads, Phi / Q / the block's T rows in LDS (p, q <= kPropCloneMaxPQ) and at most kPropCloneMaxEl elements of T per
+// thread.  The launcher, Engine::cov_propagate_clone and uvio_hp_debug_cov_propagate_p all ask this predicate.
+constexpr int kPropCloneThreads = 512, kPropCloneMaxEl = 16, kPropCloneMaxPQ = 32;
+constexpr bool prop_clone_fits(int N, int p, int q) {
+  return p <= kPropCloneMaxPQ && q <= kPropCloneMaxPQ && (long long)N * p <= kPropCloneMaxEl * kPropCloneThreads;
+}
+// launch_cov_propagate (contiguous block) + launch_clone in one launch; false (nothing launched) when
+// !prop_clone_fits(N, p, q)
 bool launch_prop_clone(hipStream_t s, double *P, int ld, int N, int s0, int p, const int *iold, int q,
                        const double *Phi, const double *Q, double *T, int src0, int dt_id, const double *dnc_dev,
                        int do_dt);

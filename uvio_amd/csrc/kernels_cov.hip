@@ -100,9 +100,8 @@ __global__ void k_clone(double *__restrict__ P, int ld, int N, int src0, int dt_
 // EKFPropagation of the contiguous block s0 .. s0+p-1 and the IMU-pose clone in ONE workgroup launch: the three
 // phases above (T, the block write, the clone) with a workgroup barrier between them instead of a kernel
 // boundary, each element computed by the same expression as in k_prop_T / k_prop_write / k_clone (so the
-// result is bit-identical).  For the propagations of N p <= 8192 and p, q <= 32
-// (cfg2-4): the frame loses two launches.
-constexpr int kPropCloneThreads = 512, kPropCloneMaxEl = 16, kPropCloneMaxPQ = 32;
+// result is bit-identical; tests/test_gpu_cov_ops.py holds both paths to the same float64 replay).  For the
+// propagations that prop_clone_fits (kernels.h: N p <= 8192 and p, q <= 32; cfg2-4): the frame loses two launches.
 __global__ void __launch_bounds__(kPropCloneThreads) k_prop_clone(double *__restrict__ P, int ld, int N, int s0, int p,
                                                                   const int *__restrict__ iold, int q,
                                                                   const double *__restrict__ Phi,
@@ -218,7 +217,7 @@ __global__ void __launch_bounds__(kPropCloneThreads) k_prop_clone(double *__rest
 bool launch_prop_clone(hipStream_t s, double *P, int ld, int N, int s0, int p, const int *iold, int q,
                        const double *Phi, const double *Q, double *T, int src0, int dt_id, const double *dnc_dev,
                        int do_dt) {
-  if (N * p > kPropCloneMaxEl * kPropCloneThreads || p > kPropCloneMaxPQ || q > kPropCloneMaxPQ) return false;
+  if (!prop_clone_fits(N, p, q)) return false;
   hipLaunchKernelGGL(k_prop_clone, dim3(1), dim3(kPropCloneThreads), 0, s, P, ld, N, s0, p, iold, q, Phi, Q, T, src0,
                      dt_id, dnc_dev, do_dt);
   return true;
@@ -250,8 +249,12 @@ void launch_marginalize(hipStream_t s, const double *P, double *Pout, int ld, in
   hipLaunchKernelGGL(k_marginalize, dim3((Nn + 127) / 128, Nn), dim3(128), 0, s, P, Pout, ld, N, m0, ms);
 }
 
-// several variables at once: Po (Nn x Nn) = P[src, src] (P is exactly symmetric: both triangles are written
-// with the same values by every update, so the gather equals the sequence of single marginalizations)
+// several variables at once: Po (Nn x Nn) = P[src, src], the plain gather of both triangles.
+// PRECONDITION: P is exactly symmetric (both triangles are written with the same values by every update;
+// Engine::marginalize_slots, the caller, relies on that).  Only then does the gather equal the sequence of single
+// marginalizations: on a P that is symmetric only up to rounding -- the IMU block right after a propagation, which
+// does not symmetrize Phi P Phi^T -- it differs from k_marginalize_multi at exactly the lower entries that kernel
+// takes from the upper triangle (tests/test_gpu_cov_ops.py pins both statements).
 __global__ void k_compact(const double *__restrict__ P, double *__restrict__ Po, int ld, int Nn, const int *__restrict__ src) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
   if (j >= Nn || i >= Nn) return;

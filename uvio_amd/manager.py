@@ -961,6 +961,68 @@ def aux_walk_p(P, ids, dims, sigma2, dt, ld=None):
     return buf
 
 
+def cov_propagate_p(P, s0, iold, Phi, Q, rows=None, clone_src=None, dt_id=-1, dnc=None, path=N.COV_PATH_AUTO, ld=None,
+                    fill=-7.25):
+    """uvio_hp_debug_cov_propagate_p: k_prop_T + k_prop_write (+ k_clone), or the fused k_prop_clone, on a standalone
+    covariance.  P (N, N); the new block starts at s0, or is the indices rows (s0 ignored); Phi (p, q) over the columns
+    iold, Q (p, p) whose upper triangle is read.  clone_src: the IMU pose's first index (None: no clone); dt_id >= 0
+    with dnc (6) adds the time-offset term.  Returns (buf, path_ran): the (N or N + 6, ld) buffer as it came back,
+    every entry outside P pre-filled with `fill`."""
+    Phi = np.ascontiguousarray(Phi, dtype=np.float64)
+    Q = np.ascontiguousarray(Q, dtype=np.float64)
+    iold = np.ascontiguousarray(iold, dtype=np.int32)
+    p, q = Phi.shape
+    if Q.shape != (p, p) or iold.shape != (q,):
+        raise ValueError("Phi (p, q), Q (p, p), iold (q)")
+    ip = C.POINTER(C.c_int)
+    rp = None
+    if rows is not None:
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        if rows.shape != (p,):
+            raise ValueError("rows (p)")
+        rp = rows.ctypes.data_as(ip)
+    if dnc is not None:
+        dnc = np.ascontiguousarray(dnc, dtype=np.float64).reshape(6)
+    P = np.asarray(P, dtype=np.float64)
+    Nn = P.shape[0]
+    nr = Nn + (6 if clone_src is not None else 0)
+    ld = nr if ld is None else int(ld)
+    buf = np.full((nr, ld), fill, dtype=np.float64)
+    buf[:Nn, :Nn] = P
+    ran = C.c_int(-1)
+    rc = N.load().uvio_hp_debug_cov_propagate_p(_dp(buf), Nn, ld, int(s0), p, rp, iold.ctypes.data_as(ip), q, _dp(Phi),
+                                                _dp(Q), 0 if clone_src is None else 1,
+                                                0 if clone_src is None else int(clone_src), int(dt_id),
+                                                None if dnc is None else _dp(dnc), int(path), C.byref(ran))
+    N.check(rc, what="uvio_hp_debug_cov_propagate_p")
+    return buf, ran.value
+
+
+def cov_gather_p(P, op, m0=0, ms=0, idx=None, ld=None, fill=-7.25):
+    """uvio_hp_debug_cov_gather_p: k_marginalize (op N.COV_MARGINALIZE, m0, ms), k_marginalize_multi / k_compact (the
+    kept indices idx) or k_marginal_gather (any idx) on a standalone covariance P (N, N) laid out at leading dimension
+    ld.  Returns the output as it came back: (Nn, ld) pre-filled with `fill` for the first three, (m, m) for the
+    gather."""
+    P = np.asarray(P, dtype=np.float64)
+    Nn = P.shape[0]
+    ld = Nn if ld is None else int(ld)
+    src = np.full((Nn, ld), fill, dtype=np.float64)
+    src[:, :Nn] = P
+    idx = np.zeros(0, dtype=np.int32) if idx is None else np.ascontiguousarray(idx, dtype=np.int32)
+    n = idx.size
+    if op == N.COV_MARGINALIZE:
+        out = np.full((max(Nn - int(ms), 0), ld), fill, dtype=np.float64)
+    elif op == N.COV_MARGINAL_GATHER:
+        out = np.full((n, n), fill, dtype=np.float64)
+    else:
+        out = np.full((n, ld), fill, dtype=np.float64)
+    outp = out if out.size else np.zeros(1)  # (a valid pointer for an empty result)
+    rc = N.load().uvio_hp_debug_cov_gather_p(_dp(src), Nn, ld, int(op), int(m0), int(ms),
+                                             idx.ctypes.data_as(C.POINTER(C.c_int)), n, _dp(outp))
+    N.check(rc, what="uvio_hp_debug_cov_gather_p")
+    return out
+
+
 def position_update_p(P, imu_id, q_GtoI, p_IinG, s, Cm, z, R, aux_id=-1, chi2_thr=float("inf"), ld=None):
     """uvio_hp_debug_position_update_p: k_fix_rows -> k_chain_M -> k_chain_update for one fix on a standalone covariance at
     the given pose.  The IMU pose's error columns start at imu_id, the lever arm s's at aux_id (< 0: a constant).
